@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- the render -> fuse hot path on synthetic data, one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config C2]
+    python bench.py [--gpus N --steps K --warmup W] [--config C2] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 A step = one pass of the hot path over one stereo view: render the L/R pair of the view from the
@@ -14,14 +14,18 @@ views with no data-path collective, then ONE RCCL reduce-scatter of the TSDF acc
 timed region (gs2mesh_amd/parallel.py).
 
 Timing: the K-step job (+ the reduction when N > 1) is timed EXACTLY as the driver contract says (barrier +
-synchronize on both sides, MAX over ranks) and REPEATED (volume reset between repeats, outside the bracket) until at
-least 5 repeats and >= 1 s of timed region have accumulated; `ms_per_step` / `value` are the MEDIAN repeat.
+synchronize on both sides, MAX over ranks).  A plain run times it ONCE: --steps K is the number of timed steps.  With
+--full it is REPEATED (volume reset between repeats, outside the bracket) until at least 5 repeats and >= 1 s of timed
+region have accumulated (--min-repeats / --min-seconds override either way); `ms_per_step` / `value` are the MEDIAN repeat.
 
 Prints ONE JSON line (rank 0): value = whole-job stereo pairs rendered+fused per second.
-Extra objects: "tsdf" (Mvoxel-updates/s), "stages" (hipEvent time per kernel launch), "roofline" (dominant kernel),
-"raster_roofline" (whole rasteriser vs SURVEY.md 8d's B_pair, with this build's instance count and with the
-reference's), "parity" (the first timed pair against the CPU oracle), "cpu_baseline" (oracle = restated Open3D 0.17
-integrate on the host cores, bounded sample), "c3" (render-only sub-measurement of the HBM-bound 2 M-Gaussian config).
+--dump-outputs DIR: after the timed job, rank 0 writes what its last step computed as DIR/*.npy (see `dump_outputs`).
+--full adds everything that is not the headline figure (off by default; the objects below are null without it):
+"steady_state" (the 2K-step job), "tsdf" (Mvoxel-updates/s), "stages" (hipEvent time per kernel launch), "roofline"
+(dominant kernel), "raster_roofline" (whole rasteriser vs SURVEY.md 8d's B_pair, with this build's instance count and
+with the reference's), "parity" (the first timed pair against the CPU oracle), "cpu_baseline" (oracle = restated Open3D
+0.17 integrate on the host cores, bounded sample), "c3" (render-only sub-measurement of the HBM-bound 2 M-Gaussian config),
+"trained_like" (render-only sub-measurement of a C2-sized model with trained-splat statistics).
 """
 import argparse
 import json
@@ -63,6 +67,49 @@ def committed_traffic(cfg_name):
         return json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))).get(cfg_name, {})
     except Exception:
         return {}
+
+
+DUMP_BYTES = 64_000_000     # --dump-outputs: all files together
+DUMP_IMAGE_BYTES = 48_000_000
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, color_pair, vol):
+    """--dump-outputs: what the timed path hands its caller after the last step, as DIR/<name>.npy (float32 / float64).
+
+      color.npy            [2,3,H,W] f32  the last step's stereo pair (left, right), as rendered; above DUMP_IMAGE_BYTES a
+                                          fixed sample of pixels instead, [2,3,m], with color_pixel_index.npy [m] (y * W + x)
+      tsdf_block_keys.npy  [n,3] f64      every allocated 16^3 block of the fused volume, sorted (x, y, z)
+      tsdf_voxel_index.npy [m] f64        the voxels of every block that are stored (x * 256 + y * 16 + z, Open3D's IndexOf):
+                                          all 4096 if they fit, else a fixed sample
+      tsdf.npy [n,m] f32, tsdf_weight.npy [n,m] f32, tsdf_rgb_sum.npy [n,m,3] f64   the voxel state of those blocks
+
+    Samples are prefixes of fixed permutations (seed DUMP_SEED), so runs with the same arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    color = color_pair.detach().float().cpu().numpy()
+    if color.nbytes > DUMP_IMAGE_BYTES:
+        n_pix = color.shape[2] * color.shape[3]
+        m = DUMP_IMAGE_BYTES // (4 * color.shape[0] * color.shape[1] + 8)
+        pix = np.sort(rng.permutation(n_pix)[:m])
+        color = np.ascontiguousarray(color.reshape(color.shape[0], color.shape[1], n_pix)[:, :, pix])
+        np.save(os.path.join(out_dir, "color_pixel_index.npy"), pix.astype(np.float64))
+        left = DUMP_BYTES - color.nbytes - pix.size * 8
+    else:
+        left = DUMP_BYTES - color.nbytes
+    np.save(os.path.join(out_dir, "color.npy"), color)
+    keys, tsdf, weight, rgb = vol.download()
+    order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+    n = len(order)
+    left -= n * 3 * 8 + 4096 * 8 + 8 * 1024           # keys, voxel index, .npy headers
+    m = max(0, min(4096, left // (32 * n))) if n else 4096      # 4 + 4 + 3 x 8 bytes per stored voxel
+    vox = np.sort(np.random.default_rng(DUMP_SEED + 1).permutation(4096)[:m])
+    sel = np.ix_(order, vox)
+    np.save(os.path.join(out_dir, "tsdf_block_keys.npy"), keys[order].astype(np.float64))
+    np.save(os.path.join(out_dir, "tsdf_voxel_index.npy"), vox.astype(np.float64))
+    np.save(os.path.join(out_dir, "tsdf.npy"), tsdf[sel])
+    np.save(os.path.join(out_dir, "tsdf_weight.npy"), weight[sel])
+    np.save(os.path.join(out_dir, "tsdf_rgb_sum.npy"), rgb[sel].astype(np.float64))
 
 
 def spatial_order_for(args, P):
@@ -239,8 +286,15 @@ def main():
                          "Gaussians), else 2: the ordered model reads its parameters once per launch and its longer compositing grids "
                          "lose less to ramp and tail (round 6: C2 3787 -> 3842, C3 2546 -> 2627, C5 3540 -> 3643 pairs/s), while an "
                          "UNORDERED model pays for eight open key arrays in the scatter (C2 3643 -> 3547); 1 = one pair per launch")
-    ap.add_argument("--min-repeats", type=int, default=5)
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="accumulated timed region to reach")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: repeated timing (median), the steady-state probe, the "
+                         "instrumented pass (stages, rooflines, TSDF rates, mesh extraction), parity vs the CPU oracle, the CPU "
+                         "baseline and the C3 / trained-like sub-measurements (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed job, write what its last step computed (rank 0) as DIR/<name>.npy, <= 64 MB in all")
+    ap.add_argument("--min-repeats", type=int, default=None, help="repeats of the timed K-step job (default: 5 with --full, else 1)")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="accumulated timed region to reach (default: 1.0 with --full, else 0)")
     ap.add_argument("--max-repeats", type=int, default=400)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -257,6 +311,10 @@ def main():
                          "buffers are staged through host memory): a dress rehearsal of the driver's multi-GPU run on a one-GPU "
                          "box -- the value it prints is NOT a scaling number")
     args = ap.parse_args()
+    if args.min_repeats is None:
+        args.min_repeats = 5 if args.full else 1
+    if args.min_seconds is None:
+        args.min_seconds = 1.0 if args.full else 0.0
     extra_raster_opts = {k: int(v) for k, v in (kv.split("=") for kv in args.raster_opts.split(",") if kv)}
     args.cull_arg = args.cull                      # as given (-1 = auto); args.cull = the level the timed configuration runs at
     if args.cull < 0:
@@ -265,7 +323,7 @@ def main():
         args.cull = auto_cull_level(_syn.CONFIGS[args.config].P)
 
     # --gpus N is the number of ranks of the job.  Under the driver's launcher (torch.distributed.run) WORLD_SIZE says the same;
-    # started plainly with --gpus N > 1 the script re-executes itself under that launcher (one rank per GPU, rendezvous on
+    # started plainly with --gpus N > 1 the script runs itself under that launcher as a child process (one rank per GPU, rendezvous on
     # 127.0.0.1); anything else -- fewer visible GPUs than ranks, a launcher world that differs from --gpus -- is an error, not
     # a silent one-GPU run that reports n_gpus: 1.
     world_env = os.environ.get("WORLD_SIZE")
@@ -283,7 +341,9 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        # a fresh child, not exec: this process has already asked the HIP runtime for the device count
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))
     if int(world_env or "1") != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world_env or 1} rank(s); "
                          "they must agree (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N)")
@@ -361,8 +421,8 @@ def main():
     gd = {k: torch.from_numpy(v).to(dev) for k, v in g.items()}
     gd["raw"] = True
     # timed views of this rank: [lo_k, lo_k + K) of the job's K_total views; the warm-up views precede them on the ring; at
-    # N = 1 another K views follow for the 2K-step job of the steady-state probe (slope between the K- and the 2K-step job)
-    probe = world == 1 and not args.no_steady_state
+    # N = 1 with --full another K views follow for the 2K-step job of the steady-state probe (slope between the K- and the 2K-step job)
+    probe = world == 1 and args.full and not args.no_steady_state
     n_local = K + Wm + (K if probe else 0)
     poses = synthetic.ring_poses(n_local, cfg.ring_radius, first=lo_k - Wm, total=max(K_total, 1))
     cams, cams_np, depths, Es = [], [], [], []
@@ -392,7 +452,8 @@ def main():
     color, rgb8 = pipe.color[0][:2], pipe._own8[0][:2]     # one pair's worth of slot 0's buffers: the serial / parity passes
 
     def step(i):
-        pipe.submit(cams[i], depths[i], Es[i], depth_scale=1.0, depth_trunc=depth_trunc, min_depth=min_depth)
+        """-> the pipeline slot whose buffers receive view i's images"""
+        return pipe.submit(cams[i], depths[i], Es[i], depth_scale=1.0, depth_trunc=depth_trunc, min_depth=min_depth)
 
     serial_imgs = ([torch.empty((Ht, Wd, 3), dtype=torch.uint8, device=dev) for _ in range(args.fuse_batch)]
                    if args.fuse_batch > 1 else [])
@@ -451,7 +512,7 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for i in range(Wm, Wm + K):
-            step(i)
+            last_slot = step(i)
         enq.append(time.perf_counter() - t0)      # host time to enqueue the K steps (no synchronisation yet)
         pipe.drain()                              # integrates the last (partial) TSDF batch, then waits for the pipeline's streams
         if exchange:
@@ -472,6 +533,11 @@ def main():
             break
     dt = statistics.median(dts)
     t_red = statistics.median(reds) if reds else None
+    if args.dump_outputs and rank == 0 and K > 0:
+        # the last timed step's stereo pair: view K - 1 of the job sits at position (K - 1) % ppl of the last chain of launches
+        # on its slot (every repeat starts with an empty group); the volume = the whole job fused (reduced when N > 1)
+        pos = (K - 1) % pairs_per_launch_used
+        dump_outputs(args.dump_outputs, pipe.color[last_slot][2 * pos:2 * pos + 2], vol)
     volume_check = None
     if args.volume_check:
         # order-independent fingerprint of the fused volume of the LAST timed job, summed over the ranks' parts (after a
@@ -525,12 +591,12 @@ def main():
                            f"(T({2 * K}) - T({K})) / {K}; fill_drain = T({K}) - {K} x steady state (pipeline fill, last TSDF sweep, final sync)")
 
     # Everything from here to the JSON line is DIAGNOSTICS of the timed job above (instrumented pass, byte models, parity, CPU baseline,
-    # sub-lines): rank 0 only -- the other ranks of a multi-GPU job go straight to the final barrier -- and behind one try / except:
+    # sub-lines): --full only, rank 0 only -- the other ranks of a multi-GPU job go straight to the final barrier -- and behind one try / except:
     # the 8-rank rehearsal (round 6) lost a rank to a division by zero in here; a diagnostic must never cost the driver its line.
     diag_error = None
     N_eye = [float(x) for x in num_rendered0]
-    tsdf, per_kernel, roofline, raster_roofline, par, cpu, c3, trained, dt_instr = None, None, None, None, None, None, None, None, 0.0
-    if rank == 0:
+    tsdf, per_kernel, roofline, raster_roofline, par, cpu, c3, trained, dt_instr = None, None, None, None, None, None, None, None, None
+    if rank == 0 and args.full:
         try:
             # ---- instrumented pass (hipEvents around every kernel launch, on the work stream) ---------
             vol.reset()
@@ -862,7 +928,8 @@ def main():
                         host_enqueue_ms_per_step=round(1e3 * statistics.median(enq) / K, 4)),   # host side of the K steps: launches only, no sync
             num_rendered_per_eye=[int(x) for x in N_eye], p_visible_per_eye=p_vis,
             tsdf=tsdf, stages=per_kernel, roofline=roofline, raster_roofline=raster_roofline, parity=par, cpu_baseline=cpu,
-            c3=c3, trained_like=trained, volume_check=volume_check, diagnostics_error=diag_error, instrumented_ms_per_step=round(1e3 * dt_instr / K, 4),
+            c3=c3, trained_like=trained, volume_check=volume_check, diagnostics_error=diag_error,
+            instrumented_ms_per_step=(round(1e3 * dt_instr / K, 4) if dt_instr is not None else None), full=bool(args.full),
             note_stages="`stages` / `roofline` / `instrumented_ms_per_step`: second pass, serial on one stream with hipEvents "
                         "around every launch, `pairs_per_launch` stereo pairs per chain of launches = the launch shapes of the "
                         "timed pass (kernels in isolation; raster `avg_us` = launch_us / pairs_per_launch, TSDF `avg_us` per frame); "

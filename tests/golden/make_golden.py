@@ -3,6 +3,7 @@
     python tests/golden/make_golden.py            # needs /root/reference, writes tests/golden/*.npz
     python tests/golden/make_golden.py --ply      # only the splat PLY fixture (the reference's save_ply, executed)
     python tests/golden/make_golden.py --open3d   # only where open3d==0.17.0 is installed: golden TSDF volume + mesh
+    python tests/golden/make_golden.py --ref-scenes   # only the digests of tests/test_oracle_vs_reference.py (oracle/_ref)
 
 The reference has no unit tests or golden vectors.  What it does have
 are independent pure-Python implementations of sub-steps of the hot path that import on CPU:
@@ -132,11 +133,41 @@ def make_open3d_golden():
     print("wrote open3d_tsdf.npz from open3d", o3d.__version__)
 
 
+def make_ref_scenes():
+    """The reference's own rasteriser kernels (oracle/_ref, compiled for the CPU by oracle/build_ref.py) on the scenes of
+    tests/test_oracle_vs_reference.py -> tests/golden/ref_scenes.json: per scene a SHA-256 digest (with dtype and shape) of
+    every input and of every output the test compares bit for bit (the per-Gaussian arrays over the visible Gaussians)."""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    sys.path.insert(0, os.path.dirname(OUT))
+    import oracle
+    import test_oracle_vs_reference as t
+    if not oracle.ref_available():
+        raise SystemExit("oracle/_ref is not built and the reference sources are absent (oracle/build_ref.py)")
+    out, cov3d = {}, None
+    for name, sc in t.scenes().items():
+        if "cov3D_precomp" in sc["kw"]:
+            sc["kw"]["cov3D_precomp"] = cov3d
+        ref = oracle.ref_forward(sc["xyz"], sc["opacity"], *sc["cam"][:3], sc["W"], sc["H"], sc["cam"][3], sc["cam"][4],
+                                 sc["bg"], **sc["kw"])
+        if name == "precomputed":
+            cov3d = ref["cov3D"]
+        if name == "ragged":
+            ref["mark_visible"] = oracle.ref_mark_visible(sc["xyz"], sc["cam"][0], sc["cam"][1])
+        out[name] = dict(inputs=t.input_digests(sc), outputs=t.output_digests(ref))
+    with open(os.path.join(OUT, "ref_scenes.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote ref_scenes.json:", len(out), "scenes")
+
+
 def main():
     if "--open3d" in sys.argv:
         return make_open3d_golden()
     if "--ply" in sys.argv:
         return make_ply_fixture()
+    if "--ref-scenes" in sys.argv:
+        return make_ref_scenes()
     sh_utils, graphics_utils, general_utils, tu = _import_reference()
     rng = np.random.default_rng(20240611)
 
@@ -267,6 +298,7 @@ def main():
         campos=np.asarray(cam.camera_center, np.float32), tanfovx=cam.tanfovx, tanfovy=cam.tanfovy,
         **{"out_" + k: v for k, v in ref.items() if k != "num_rendered"}, out_num_rendered=ref["num_rendered"])
     make_ply_fixture()
+    make_ref_scenes()
     print("golden fixtures written to", OUT)
 
 

@@ -93,3 +93,10 @@ def test_launch_shape_rules_of_the_timed_pass():
     import numpy as np
     assert auto_blend_mode(dict(opacity=np.array([5.0, 5.0, -1.0, 0.0], np.float32), raw=True)) == 3      # half of them above logit(0.98)
     assert auto_blend_mode(dict(opacity=np.array([0.5, 0.97], np.float32))) == 2
+
+
+def test_plain_and_full_options_are_declared():
+    """`--full` switches the diagnostics on, `--dump-outputs DIR` writes the last step's outputs; both parse without a GPU."""
+    r = _run_bench(["--help"], timeout=120)
+    assert r.returncode == 0, r.stderr[-500:]
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout and "--steps" in r.stdout
