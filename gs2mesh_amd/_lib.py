@@ -101,6 +101,10 @@ _PROTOS = {
     "gs2m_tsdf_block_map": (i32, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, i32, i64, i64, i32, vp, vp]),
     "gs2m_tsdf_map_keys": (i32, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, vp, vp, i64, C.POINTER(C.c_uint8), vp]),
     "gs2m_tsdf_unpack": (i32, [vp, vp, i64, i32, vp, vp, i32, vp]),
+    "gs2m_png_create": (i32, [C.POINTER(vp), i32]),
+    "gs2m_png_destroy": (i32, [vp]),
+    "gs2m_png_max_bytes": (i64, [i32, i32, i32]),
+    "gs2m_png_encode": (i32, [vp, i32, i32, i32, vp, i64, vp, i64, vp, i32, i32, vp]),
 }
 
 SYMBOLS = tuple(_PROTOS)

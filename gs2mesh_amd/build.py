@@ -27,6 +27,7 @@ SOURCES = [
     ("tsdf_kernels.hip", ["-ffp-contract=off"]),
     ("tsdf_api.hip", []),
     ("stereo_kernels.hip", ["-ffp-contract=off"]),
+    ("png_encode.hip", []),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", os.path.join(CSRC, "hip"), "-I", CSRC,
           "-Wall", "-Wno-unused-function"]

@@ -13,7 +13,10 @@ unchanged.  What changes underneath:
     3DGS ``Scene`` that loads every training image just to reach ``load_ply``
     (GS/scene/__init__.py:71-81);
   * ``render_pair_device`` is the in-memory hand-off: u8 HWC images on the device,
-    quantised exactly as ``cv2.imwrite`` would (round-half-even, saturate).
+    quantised exactly as ``cv2.imwrite`` would (round-half-even, saturate);
+  * ``png_encoder="device"`` (or ``args.png_encoder = "device"``) makes the PNG files on the GPU
+    (``gs2mesh_amd.png``): only the compressed bytes leave the device; ``render_image_pairs`` renders up to
+    four pairs per launch and writes the files from a writer thread.  ``"pil"`` (the default) is the PIL path.
 """
 from __future__ import annotations
 
@@ -31,6 +34,7 @@ from .graphics import Camera
 from .poses import (RT_from_rot_pos, calculate_right_camera_pose, convert_R_T_to_GS, eul2rotm,
                     intrinsic_from_camera_params, rotm2eul)
 from . import _lib
+from .png import write_file
 from .rasterizer import Rasterizer, camera_from
 
 
@@ -58,8 +62,16 @@ def sort_camera_coordinates(coordinates):
 
 
 class Renderer:
+    PAIRS_PER_LAUNCH = 4     # render_image_pairs: the launch shape RenderFusePipeline(pairs_per_launch=4) times
+
     def __init__(self, base_dir, colmap_dir, output_dir_root, args, dataset='custom', splatting='custom',
-                 experiment_name=None, device='cuda'):
+                 experiment_name=None, device='cuda', *, png_encoder=None):
+        self.png_encoder = png_encoder if png_encoder is not None else getattr(args, "png_encoder", "pil")
+        if self.png_encoder not in ("pil", "device"):
+            raise ValueError(f"png_encoder must be 'pil' or 'device', got {self.png_encoder!r}")
+        self._png = None        # PngEncoder / PngWriter of the device path, made on first use
+        self._writer = None
+        self._dirs = set()      # output directories known to exist
         self.args = args
         self.render_name = args.colmap_name
         self.white_background = args.GS_white_background
@@ -195,7 +207,9 @@ class Renderer:
 
     def render_image_pair(self, camera_number, visualize=False):
         """Render the stereo pair of view `camera_number` and write left.png / right.png
-        (renderer_utils.py:363-395)."""
+        (renderer_utils.py:363-395).  Both files are complete on return."""
+        if self.png_encoder == "device":
+            return self._render_image_pair_device(camera_number, visualize)
         from PIL import Image as PILImage
         res = self.render_pair_device(camera_number)
         rgb8 = res["rgb8"].cpu().numpy()
@@ -208,3 +222,57 @@ class Renderer:
             plt.imshow(rgb8[0])
             plt.imshow(rgb8[1], alpha=0.5)
             plt.show()
+
+    # -- device PNG path (png_encoder="device", render_image_pairs) ------------------------------------------------------
+    def _out_dir(self, camera_number):
+        d = self.render_folder_name(camera_number)
+        if d not in self._dirs:
+            os.makedirs(d, exist_ok=True)
+            self._dirs.add(d)
+        return d
+
+    def _encoder(self):
+        if self._raster is None:
+            raise RuntimeError("call prepare_renderer() first")
+        if self._png is None:
+            from .png import PngEncoder
+            self._png = PngEncoder(self._raster.device)
+        return self._png
+
+    def _render_image_pair_device(self, camera_number, visualize):
+        """Both eyes encoded in one gs2m_png_encode call; only the compressed bytes leave the GPU."""
+        res = self.render_pair_device(camera_number)
+        files = self._encoder().encode(res["rgb8"])
+        out_dir = self._out_dir(camera_number)
+        for name, data in zip(('left', 'right'), files):
+            write_file(os.path.join(out_dir, f'{name}.png'), data)
+        if visualize:
+            import matplotlib.pyplot as plt
+            rgb8 = res["rgb8"].cpu().numpy()
+            plt.imshow(rgb8[0])
+            plt.imshow(rgb8[1], alpha=0.5)
+            plt.show()
+
+    def render_image_pairs(self, camera_numbers, wait=True):
+        """left.png / right.png of every view in `camera_numbers` (the same files as ``render_image_pair`` with
+        png_encoder="device"): up to PAIRS_PER_LAUNCH pairs per render_views call, their images encoded in one call and
+        written by a writer thread.  ``wait=False`` returns once everything is enqueued; ``flush()`` waits for the files."""
+        cams = list(camera_numbers)
+        if self._writer is None:
+            from .png import PngWriter
+            self._writer = PngWriter(self._encoder())
+        for i in range(0, len(cams), self.PAIRS_PER_LAUNCH):
+            group = cams[i:i + self.PAIRS_PER_LAUNCH]
+            views = [v for c in group for v in self._pair(c)]
+            with torch.no_grad():
+                res = self._raster.render_views(self.gaussians.raw(), views, bg=self._bg_host, want_color=False,
+                                                want_rgb8=True)
+            paths = [os.path.join(self._out_dir(c), f'{name}.png') for c in group for name in ('left', 'right')]
+            self._writer.submit(paths, res["rgb8"])
+        if wait:
+            self._writer.flush()
+
+    def flush(self):
+        """Wait until every file ``render_image_pairs`` enqueued is on disk (re-raises a write error)."""
+        if self._writer is not None:
+            self._writer.flush()

@@ -491,6 +491,31 @@ int gs2m_stereo_depth_occlusion(const float* disp_lr, const float* disp_rl, int 
                                 double fx_times_baseline, double occlusion_threshold, float* depth_out,
                                 uint8_t* mask_out, gs2m_stream stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* PNG encoder (the Renderer's left.png / right.png)               */
+/* ------------------------------------------------------------------------------------ */
+
+/*
+ * Replaces the PIL / cv2 PNG writes of Renderer.render_image_pair (gs2mesh_utils/renderer_utils.py:389-390): the files are
+ * made on the device and only the compressed bytes cross to the host.  The stream (gs2mesh_amd/csrc/png_encode.hip):
+ * 8-bit RGB, IHDR / one IDAT / IEND; filter `filter` on every row; the filtered scanlines cut into segments of
+ * rows_per_segment rows, each one deflate block with a dynamic Huffman code of its own (literals only, lengths <= 15)
+ * followed by an empty stored block, or stored blocks when that is not smaller.  Output bytes depend only on the pixels,
+ * rows_per_segment and filter (the same on every device and batch size).
+ *   gs2m_png_max_bytes  upper bound of one file (every segment stored); -1 for sizes it cannot encode.
+ *   gs2m_png_encode     rgb8: device [n, H, W, 3] u8 (image k at rgb8 + k*image_stride bytes); out: device [n, out_stride]
+ *                       u8 with out_stride >= gs2m_png_max_bytes; out_bytes: device [n] int64, file k = out[k, :out_bytes[k]].
+ *                       filter: 0 (none) or 4 (Paeth, default); rows_per_segment: >= 1 (default 16).
+ *                       Stream-ordered, no host synchronisation; the handle's grow-only scratch is allocated on the
+ *                       first call at a size (that call synchronises).
+ */
+typedef struct gs2m_png gs2m_png;
+int gs2m_png_create(gs2m_png** out, int device);
+int gs2m_png_destroy(gs2m_png* p);
+int64_t gs2m_png_max_bytes(int width, int height, int rows_per_segment);
+int gs2m_png_encode(gs2m_png* p, int n, int width, int height, const uint8_t* rgb8, int64_t image_stride, uint8_t* out,
+                    int64_t out_stride, int64_t* out_bytes, int filter, int rows_per_segment, gs2m_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
