@@ -78,6 +78,7 @@ _PROTOS = {
     "gs2m_tsdf_extract": (i32, [vp, vp, i64, vp, vp, C.POINTER(i64)]),
     "gs2m_tsdf_extract_indexed": (i32, [vp, vp, i64, vp, vp, vp, C.POINTER(i64)]),
     "gs2m_stereo_depth_occlusion": (i32, [vp, vp, i32, i32, f64, f64, vp, vp, vp]),
+    "gs2m_mask_preprocess": (i32, [i32, i32, i32, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, C.POINTER(vp), vp, vp]),
     "gs2m_tsdf_create": (i32, [C.POINTER(vp), f64, f64, i32, i32, i32, i64, i32]),
     "gs2m_tsdf_destroy": (i32, [vp]),
     "gs2m_tsdf_reset": (i32, [vp, vp]),
@@ -96,6 +97,7 @@ _PROTOS = {
     "gs2m_tsdf_extract_mesh": (i32, [vp, vp, C.POINTER(i64), C.POINTER(i64)]),
     "gs2m_tsdf_mesh_copy": (i32, [vp, vp, vp, vp, vp, vp]),
     "gs2m_mesh_cluster": (i32, [i32, vp, i64, vp, vp, vp, C.POINTER(i64)]),
+    "gs2m_mesh_vertex_normals": (i32, [i32, vp, i64, vp, i64, vp, vp, vp]),
     "gs2m_tsdf_replace": (i32, [vp, vp, i64, i32, vp, vp, vp]),
     "gs2m_tsdf_map_bytes": (i64, [C.POINTER(C.c_int32), i32]),
     "gs2m_tsdf_block_map": (i32, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, i32, i64, i64, i32, vp, vp]),
@@ -158,6 +160,13 @@ class DeviceMemory:
         tdt = {"float32": torch.float32, "float64": torch.float64, "int32": torch.int32, "uint32": torch.int32,
                "int64": torch.int64, "uint8": torch.uint8}[np.dtype(np_dtype).name]
         return torch.zeros(tuple(shape), dtype=tdt, device=self.buffer_device(device))
+
+    def empty(self, shape, np_dtype, device):
+        """uninitialised buffer on ``device`` for results a kernel writes in full (``zeros`` without the fill)"""
+        import torch
+        tdt = {"float32": torch.float32, "float64": torch.float64, "int32": torch.int32, "uint32": torch.int32,
+               "int64": torch.int64, "uint8": torch.uint8}[np.dtype(np_dtype).name]
+        return torch.empty(tuple(shape), dtype=tdt, device=self.buffer_device(device))
 
     def upload(self, a, torch_dtype, device):
         """host array or tensor -> contiguous device tensor of ``torch_dtype``"""

@@ -255,3 +255,108 @@ k_mesh_uf_labels(unsigned n_tri, const unsigned* __restrict__ root, const unsign
         }
     }
 }
+
+// ---- vertex normals (TriangleMesh.compute_vertex_normals, tsdf_utils.py:110) ----------------------------------------------------
+// Bit-identical to the numpy statement in gs2mesh_amd/mesh.py (this header is compiled with -ffp-contract=off):
+//   triangle t:  n = np.cross(v1 - v0, v2 - v0);  n / (|n| > 0 ? |n| : 1),  |n| = sqrt((x*x + y*y) + z*z)  (np.linalg.norm)
+//   vertex v:    the sum, from 0.0, of the normals of its incidences in np.add.at order -- every (t, k = 0) with tri[t][0] == v in
+//                ascending t, then k = 1, then k = 2 -- normalised the same way.
+// The order is the incidence number i = k * n_tri + t.  The incidences are bucketed by vertex with atomics (arbitrary order inside
+// a bucket), then every bucket is sorted by i with merge passes of doubling width (runs never cross a bucket; ceil(log2(max
+// degree)) passes: any degree), and one thread per vertex sums its bucket in that order.
+GS2M_DEVICE double mesh_norm3(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
+GS2M_DEVICE bool mesh_tri_ok(const int* __restrict__ tri, size_t t, unsigned nv) {
+    return (unsigned)tri[3 * t] < nv && (unsigned)tri[3 * t + 1] < nv && (unsigned)tri[3 * t + 2] < nv;
+}
+// triangle normals + vertex degrees; bad[0] = 1 when a triangle names a vertex outside [0, nv) (the triangle is skipped)
+GS2M_KERNEL void __launch_bounds__(256)
+k_mesh_tri_normals(const double* __restrict__ v, unsigned nv, const int* __restrict__ tri, unsigned nt, double* __restrict__ tn,
+                   unsigned* __restrict__ deg, unsigned* __restrict__ bad) {
+    for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < nt; t += gridDim.x * 256u) {
+        if (!mesh_tri_ok(tri, t, nv)) {
+            atomicOr(bad, 1u);
+            continue;
+        }
+        const size_t i0 = (size_t)tri[3 * (size_t)t], i1 = (size_t)tri[3 * (size_t)t + 1], i2 = (size_t)tri[3 * (size_t)t + 2];
+        const double a0 = v[3 * i1] - v[3 * i0], a1 = v[3 * i1 + 1] - v[3 * i0 + 1], a2 = v[3 * i1 + 2] - v[3 * i0 + 2];
+        const double b0 = v[3 * i2] - v[3 * i0], b1 = v[3 * i2 + 1] - v[3 * i0 + 1], b2 = v[3 * i2 + 2] - v[3 * i0 + 2];
+        const double c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;
+        const double ln = mesh_norm3(c0, c1, c2);
+        const double d = ln > 0.0 ? ln : 1.0;
+        tn[3 * (size_t)t] = c0 / d;
+        tn[3 * (size_t)t + 1] = c1 / d;
+        tn[3 * (size_t)t + 2] = c2 / d;
+        atomicAdd(&deg[i0], 1u);
+        atomicAdd(&deg[i1], 1u);
+        atomicAdd(&deg[i2], 1u);
+    }
+}
+GS2M_KERNEL void __launch_bounds__(256)
+k_mesh_deg_max(const unsigned* __restrict__ deg, unsigned nv, unsigned* __restrict__ max_deg) {
+    unsigned m = 0u;
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < nv; i += gridDim.x * 256u) m = deg[i] > m ? deg[i] : m;
+    if (m) atomicMax(max_deg, m);
+}
+// incidence i = k * nt + t into the bucket of its vertex (off = exclusive scan of deg; fill starts at 0); owner[slot] = vertex
+GS2M_KERNEL void __launch_bounds__(256)
+k_mesh_incidence_scatter(const int* __restrict__ tri, unsigned nv, unsigned nt, const unsigned* __restrict__ off, unsigned* __restrict__ fill,
+                         unsigned* __restrict__ list, unsigned* __restrict__ owner) {
+    const unsigned n = 3u * nt;
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const unsigned k = i / nt, t = i - k * nt;
+        if (!mesh_tri_ok(tri, t, nv)) continue;
+        const unsigned vtx = (unsigned)tri[3 * (size_t)t + k];
+        const unsigned slot = off[vtx] + atomicAdd(&fill[vtx], 1u);
+        list[slot] = i;
+        owner[slot] = vtx;
+    }
+}
+// one merge pass: inside every bucket, runs of `width` sorted entries are merged pairwise (src -> dst).  Entry x of run r lands
+// at its index in the run + the number of entries of the partner run below it (the entries of a bucket are distinct).
+GS2M_KERNEL void __launch_bounds__(256)
+k_mesh_bucket_merge(unsigned n, unsigned width, const unsigned* __restrict__ off, const unsigned* __restrict__ deg,
+                    const unsigned* __restrict__ owner, const unsigned* __restrict__ src, unsigned* __restrict__ dst) {
+    for (unsigned p = blockIdx.x * 256u + threadIdx.x; p < n; p += gridDim.x * 256u) {
+        const unsigned vtx = owner[p], s = off[vtx], len = deg[vtx];
+        const unsigned q = p - s, r = q / width, x = src[p];
+        const unsigned long long pair = (unsigned long long)(r & ~1u) * width;
+        unsigned long long lo = (r & 1u) ? pair : pair + width;
+        unsigned long long hi = (r & 1u) ? pair + width : pair + 2ull * width;
+        hi = hi < len ? hi : len;
+        lo = lo < hi ? lo : hi;
+        unsigned below = 0u;     // lower bound of x in the partner run [lo, hi)
+        unsigned long long a = lo, b = hi;
+        while (a < b) {
+            const unsigned long long m = (a + b) >> 1;
+            if (src[s + m] < x) a = m + 1;
+            else b = m;
+        }
+        below = (unsigned)(a - lo);
+        dst[s + (unsigned)pair + (q - r * width) + below] = x;
+    }
+}
+// per vertex: the sum of its incidences' triangle normals in bucket (= np.add.at) order, normalised.  One thread walks the whole
+// bucket: the additions are a serial chain by definition (floating-point addition does not associate, and the result must be the
+// one np.add.at's left-to-right sum rounds to), so a vertex of degree d costs d dependent adds -- a tree or segmented reduction
+// would round differently.  The loads of the chain do not depend on the sum and run ahead of it.  Marching-cubes meshes have
+// degrees of about 6; a mesh with one vertex of very high degree makes this launch as long as that vertex's chain.
+GS2M_KERNEL void __launch_bounds__(256)
+k_mesh_vertex_sum(unsigned nv, unsigned nt, const unsigned* __restrict__ off, const unsigned* __restrict__ deg,
+                  const unsigned* __restrict__ list, const double* __restrict__ tn, double* __restrict__ vn) {
+    for (unsigned vtx = blockIdx.x * 256u + threadIdx.x; vtx < nv; vtx += gridDim.x * 256u) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        const unsigned b = off[vtx], e = b + deg[vtx];
+        for (unsigned j = b; j < e; ++j) {
+            const unsigned i = list[j];
+            const size_t t = i - (i / nt) * nt;
+            s0 += tn[3 * t];
+            s1 += tn[3 * t + 1];
+            s2 += tn[3 * t + 2];
+        }
+        const double ln = mesh_norm3(s0, s1, s2);
+        const double d = ln > 0.0 ? ln : 1.0;
+        vn[3 * (size_t)vtx] = s0 / d;
+        vn[3 * (size_t)vtx + 1] = s1 / d;
+        vn[3 * (size_t)vtx + 2] = s2 / d;
+    }
+}

@@ -15,6 +15,7 @@
 
 #include "../../include/gs2mesh_amd.h"
 #include "platform.h"
+#include "mask_kernels.h"
 
 void gs2m_set_error(const char* fmt, ...);
 
@@ -46,5 +47,48 @@ extern "C" int gs2m_stereo_depth_occlusion(const float* disp_lr, const float* di
     }
     GS2M_LAUNCH(k_stereo_depth_occlusion, dim3((width + 255) / 256, height), dim3(256), 0, stream, disp_lr, disp_rl,
                 width, height, (float)fx_times_baseline, occlusion_threshold, depth_out, mask_out);
+    return 0;
+}
+
+extern "C" int gs2m_mask_preprocess(int n, int width, int height, const uint8_t* const* object_masks,
+                                    const uint8_t* const* occlusion_masks, int invert, int erode, int closing_k, int erosion_k,
+                                    uint8_t* const* out_masks, uint64_t* scratch, gs2m_stream stream) {
+    if (n < 0 || width <= 0 || height <= 0 || (n > 0 && !out_masks)) {
+        gs2m_set_error("gs2m_mask_preprocess: bad argument");
+        return 1;
+    }
+    if (closing_k < 1 || erosion_k < 1) {
+        gs2m_set_error("gs2m_mask_preprocess: kernel sizes must be >= 1 (closing %d, erosion %d)", closing_k, erosion_k);
+        return 1;
+    }
+    const size_t frame_words = (size_t)height * (size_t)((width + 63) / 64);
+    for (int i = 0; i < n; ++i) {
+        const bool obj = object_masks && object_masks[i], occ = occlusion_masks && occlusion_masks[i];
+        if ((obj || occ) && !out_masks[i]) {
+            gs2m_set_error("gs2m_mask_preprocess: frame %d has an input mask but no output", i);
+            return 1;
+        }
+        if (obj && erode && !scratch) {
+            gs2m_set_error("gs2m_mask_preprocess: the closing / erosion needs scratch");
+            return 1;
+        }
+    }
+    for (int f0 = 0; f0 < n; f0 += GS2M_MASK_BATCH) {
+        const int nf = n - f0 < GS2M_MASK_BATCH ? n - f0 : GS2M_MASK_BATCH;
+        MaskBatch B;
+        bool any = false;
+        for (int i = 0; i < GS2M_MASK_BATCH; ++i) {
+            const bool in = i < nf;
+            B.obj[i] = in && object_masks ? object_masks[f0 + i] : nullptr;
+            B.occ[i] = in && occlusion_masks ? occlusion_masks[f0 + i] : nullptr;
+            B.out[i] = in && (B.obj[i] || B.occ[i]) ? out_masks[f0 + i] : nullptr;
+            any = any || B.out[i];
+        }
+        if (!any) continue;
+        // scratch of this chunk: two bitmaps of nf frames, after those of the chunks before it
+        unsigned long long* a_bits = scratch ? (unsigned long long*)scratch + 2 * (size_t)f0 * frame_words : nullptr;
+        unsigned long long* b_bits = a_bits ? a_bits + (size_t)nf * frame_words : nullptr;
+        gs2m_launch_mask_preprocess((hipStream_t)stream, B, nf, width, height, invert, erode, closing_k, erosion_k, a_bits, b_bits);
+    }
     return 0;
 }

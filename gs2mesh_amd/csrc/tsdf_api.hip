@@ -891,3 +891,69 @@ extern "C" int gs2m_mesh_cluster(int device, gs2m_stream stream, int64_t n_trian
     *n_clusters = (int64_t)total;
     return 0;
 }
+
+extern "C" int gs2m_mesh_vertex_normals(int device, gs2m_stream stream, int64_t n_vertices, const double* vertices, int64_t n_triangles,
+                                        const int32_t* triangles, double* triangle_normals, double* vertex_normals) {
+    if (n_vertices < 0 || n_vertices > 0x7fffffff || n_triangles < 0 || n_triangles > 0x2aaaaaaa || (n_vertices > 0 && !vertex_normals) ||
+        (n_triangles > 0 && (!vertices || !triangles || !triangle_normals))) {
+        gs2m_set_error("gs2m_mesh_vertex_normals: bad argument");
+        return 1;
+    }
+    if (device < 0 || device >= 64) {
+        gs2m_set_error("gs2m_mesh_vertex_normals: device %d not in 0..63", device);
+        return 1;
+    }
+    if (n_vertices == 0 && n_triangles == 0) return 0;
+    if (n_vertices == 0) {
+        gs2m_set_error("gs2m_mesh_vertex_normals: %lld triangles and no vertices", (long long)n_triangles);
+        return 1;
+    }
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (n_triangles == 0) {
+        HIPCHK(hipMemsetAsync(vertex_normals, 0, sizeof(double) * 3 * (size_t)n_vertices, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    }
+    const unsigned nv = (unsigned)n_vertices, nt = (unsigned)n_triangles, ni = 3u * nt;
+    const unsigned m = (nv + 4095u) / 4096u;
+    std::lock_guard<std::mutex> hold(g_cluster_lock);          // the per-device arena of gs2m_mesh_cluster (both calls synchronise)
+    Arena A(&g_cluster_scratch[device].p, &g_cluster_scratch[device].cap);
+    const size_t need = 3 * Arena::pad(sizeof(unsigned) * (size_t)nv) + 3 * Arena::pad(sizeof(unsigned) * (size_t)ni) +
+                        Arena::pad(sizeof(unsigned) * ((size_t)m + 2)) + Arena::pad(sizeof(unsigned) * 2);
+    if (!A.reserve(need)) {
+        gs2m_set_error("gs2m_mesh_vertex_normals: out of device memory for %u triangles", nt);
+        return 1;
+    }
+    unsigned* deg = A.take<unsigned>(nv);
+    unsigned* off = A.take<unsigned>(nv);
+    unsigned* fill = A.take<unsigned>(nv);
+    unsigned* list = A.take<unsigned>(ni);
+    unsigned* list2 = A.take<unsigned>(ni);
+    unsigned* owner = A.take<unsigned>(ni);
+    unsigned* scratch = A.take<unsigned>((size_t)m + 2);
+    unsigned* small = A.take<unsigned>(2);      // {bad index, largest degree}
+    HIPCHK(hipMemsetAsync(deg, 0, sizeof(unsigned) * (size_t)nv, st));
+    HIPCHK(hipMemsetAsync(fill, 0, sizeof(unsigned) * (size_t)nv, st));
+    HIPCHK(hipMemsetAsync(small, 0, sizeof(unsigned) * 2, st));
+    gs2m_launch_mesh_normals_bucket(st, vertices, nv, triangles, nt, triangle_normals, deg, off, fill, list, owner, scratch, small);
+    unsigned h_small[2] = {0u, 0u};
+    HIPCHK(hipMemcpyAsync(h_small, small, sizeof(h_small), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (h_small[0]) {
+        gs2m_set_error("gs2m_mesh_vertex_normals: a triangle names a vertex outside 0..%u", nv - 1);
+        return 1;
+    }
+    for (unsigned width = 1u; width < h_small[1]; width *= 2u) {
+        gs2m_launch_mesh_bucket_merge(st, ni, width, off, deg, owner, list, list2);
+        unsigned* t = list;
+        list = list2;
+        list2 = t;
+        if (width > 0x7fffffffu) break;
+    }
+    gs2m_launch_mesh_vertex_sum(st, nv, nt, off, deg, list, triangle_normals, vertex_normals);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return 0;
+}

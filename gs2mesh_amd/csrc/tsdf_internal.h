@@ -37,4 +37,10 @@ void gs2m_launch_mesh_weld_emit(hipStream_t st, unsigned n, const unsigned* hfir
 void gs2m_launch_mesh_cluster(hipStream_t st, const int* tri, unsigned n_tri, unsigned long long* hkeys, unsigned* hval, unsigned cap,
                               unsigned* parent, unsigned* root, unsigned* flag, unsigned* pos, unsigned* scratch, int* labels,
                               unsigned long long* cluster_n);
+void gs2m_launch_mesh_normals_bucket(hipStream_t st, const double* verts, unsigned nv, const int* tri, unsigned nt, double* tn, unsigned* deg,
+                                     unsigned* off, unsigned* fill, unsigned* list, unsigned* owner, unsigned* scratch, unsigned* small);
+void gs2m_launch_mesh_bucket_merge(hipStream_t st, unsigned n, unsigned width, const unsigned* off, const unsigned* deg, const unsigned* owner,
+                                   const unsigned* src, unsigned* dst);
+void gs2m_launch_mesh_vertex_sum(hipStream_t st, unsigned nv, unsigned nt, const unsigned* off, const unsigned* deg, const unsigned* list,
+                                 const double* tn, double* vn);
 void gs2m_set_error(const char* fmt, ...);

@@ -120,3 +120,19 @@ void gs2m_launch_mesh_cluster(hipStream_t st, const int* tri, unsigned n_tri, un
     gs2m_launch_scan_u32(st, flag, n_tri, pos, scratch);
     GS2M_LAUNCH(k_mesh_uf_labels, dim3(grid_for(n_tri)), dim3(256), 0, st, n_tri, root, pos, labels, cluster_n);
 }
+// vertex normals, first half: triangle normals, degrees, their scan (total -> scratch[ceil(nv / 4096)]), the largest degree, buckets
+void gs2m_launch_mesh_normals_bucket(hipStream_t st, const double* verts, unsigned nv, const int* tri, unsigned nt, double* tn, unsigned* deg,
+                                     unsigned* off, unsigned* fill, unsigned* list, unsigned* owner, unsigned* scratch, unsigned* small) {
+    GS2M_LAUNCH(k_mesh_tri_normals, dim3(grid_for(nt)), dim3(256), 0, st, verts, nv, tri, nt, tn, deg, small);
+    gs2m_launch_scan_u32(st, deg, nv, off, scratch);
+    GS2M_LAUNCH(k_mesh_deg_max, dim3(grid_for(nv)), dim3(256), 0, st, deg, nv, small + 1);
+    GS2M_LAUNCH(k_mesh_incidence_scatter, dim3(grid_for(3u * nt)), dim3(256), 0, st, tri, nv, nt, off, fill, list, owner);
+}
+void gs2m_launch_mesh_bucket_merge(hipStream_t st, unsigned n, unsigned width, const unsigned* off, const unsigned* deg, const unsigned* owner,
+                                   const unsigned* src, unsigned* dst) {
+    GS2M_LAUNCH(k_mesh_bucket_merge, dim3(grid_for(n)), dim3(256), 0, st, n, width, off, deg, owner, src, dst);
+}
+void gs2m_launch_mesh_vertex_sum(hipStream_t st, unsigned nv, unsigned nt, const unsigned* off, const unsigned* deg, const unsigned* list,
+                                 const double* tn, double* vn) {
+    GS2M_LAUNCH(k_mesh_vertex_sum, dim3(grid_for(nv)), dim3(256), 0, st, nv, nt, off, deg, list, tn, vn);
+}

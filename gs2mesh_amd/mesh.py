@@ -59,14 +59,42 @@ class TriangleMesh:
         self.triangle_normals = n / np.where(ln > 0, ln, 1.0)
         return self
 
-    def compute_vertex_normals(self):
-        """Open3D ComputeVertexNormals: sum of the (normalised) normals of the adjacent triangles, normalised."""
+    def compute_vertex_normals(self, on_device=False, lib=None, device=None):
+        """Open3D ComputeVertexNormals: sum of the (normalised) normals of the adjacent triangles, normalised.  ``on_device``:
+        the same arithmetic on the GPU (``gs2m_mesh_vertex_normals``, bit-identical to the numpy statement below), on the
+        triangle indices the extraction left on the device when this mesh still is that mesh, else on an upload of
+        ``triangles``."""
+        if on_device:
+            return self._vertex_normals_device(lib, device)
         self.compute_triangle_normals()
         vn = np.zeros_like(self.vertices)
         for k in range(3):
             np.add.at(vn, self.triangles[:, k], self.triangle_normals)
         ln = np.linalg.norm(vn, axis=1, keepdims=True)
         self.vertex_normals = vn / np.where(ln > 0, ln, 1.0)
+        return self
+
+    def _vertex_normals_device(self, lib, device):
+        import ctypes as C
+        from . import _lib
+        import torch
+        nv, nt = int(self.vertices.shape[0]), int(self.triangles.shape[0])
+        dev = getattr(self, "_dev", None)
+        if dev is not None and dev[3] is self.triangles and lib in (None, dev[1]):
+            tri_dev, lib, device = dev[0], dev[1], dev[2]
+        else:
+            lib = lib if lib is not None else _lib.get()
+            if device is None:
+                device = torch.cuda.current_device() if torch.cuda.is_available() else 0
+            tri_dev = _lib.MEMORY.upload(np.ascontiguousarray(self.triangles, np.int32), torch.int32, device) if nt else None
+        # handed over as a tensor: every memory policy uploads an f64 tensor as it is
+        v_dev = _lib.MEMORY.upload(torch.from_numpy(np.ascontiguousarray(self.vertices, np.float64)), torch.float64, device) if nv else None
+        tn_dev = _lib.MEMORY.zeros((nt, 3), np.float64, device)
+        vn_dev = _lib.MEMORY.zeros((nv, 3), np.float64, device)
+        _lib.check(lib.gs2m_mesh_vertex_normals(int(device), _lib.MEMORY.current_stream(device), nv, _lib.MEMORY.ptr(v_dev), nt,
+                                                _lib.MEMORY.ptr(tri_dev), _lib.MEMORY.ptr(tn_dev), _lib.MEMORY.ptr(vn_dev)), lib)
+        self.triangle_normals = np.asarray(_lib.MEMORY.download(tn_dev), np.float64).reshape(nt, 3)
+        self.vertex_normals = np.asarray(_lib.MEMORY.download(vn_dev), np.float64).reshape(nv, 3)
         return self
 
     # ---- device attachment -------------------------------------------------------------------

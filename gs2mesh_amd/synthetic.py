@@ -7,6 +7,7 @@ shapes: ``synth_v1`` Gaussians, ring-of-cameras stereo poses, analytic sphere de
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -192,3 +193,48 @@ def sphere_depth_torch(pose_w2c, width, height, fx, fy, cx, cy, radius, device):
     s = torch.where(hit, (-b - torch.sqrt(torch.clamp(disc, min=0.0))) / (2 * a), torch.zeros_like(a))
     s = torch.where(s > 0, s, torch.zeros_like(s))
     return s.to(torch.float32).contiguous()
+
+
+class DiskScene:
+    """The part of ``Renderer`` that ``TSDF`` reads (left cameras, baseline, render folders) for a scene written by
+    ``write_tsdf_scene``."""
+
+    def __init__(self, root, poses, width, height, focal, baseline):
+        self.output_dir_root = root
+        self.baseline = baseline
+        self.left_cameras = []
+        for p in poses:
+            E = np.eye(4)
+            E[:3] = p
+            self.left_cameras.append(dict(width=width, height=height, fx=focal, fy=focal, cx=width / 2.0, cy=height / 2.0,
+                                          extrinsic=np.linalg.inv(E)))
+
+    def __len__(self):
+        return len(self.left_cameras)
+
+    def render_folder_name(self, i):
+        return os.path.join(self.output_dir_root, f"{i:03}")
+
+
+def write_tsdf_scene(root, n_views, width, height, focal, seed, model_name="DLNR_Middlebury", sphere_radius=0.6,
+                     ring_radius=3.5, baseline_pct=7.0):
+    """The on-disk layout ``TSDF.run`` reads for n_views views on a ring around a sphere: ``<root>/<i:03>/left.png`` (colour
+    pattern), ``out_<model>/depth.npy`` (analytic sphere depth, seeded noise), ``left_mask.npy`` (the sphere's silhouette with
+    seeded holes) and ``out_<model>/occlusion_mask.npy`` (seeded, ~5 % occluded).  Returns a ``DiskScene``."""
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    poses = ring_poses(n_views, ring_radius)
+    scene = DiskScene(root, poses, width, height, focal, ring_radius * baseline_pct / 100.0)
+    base = color_pattern(width, height)
+    for i, p in enumerate(poses):
+        d = scene.render_folder_name(i)
+        os.makedirs(os.path.join(d, f"out_{model_name}"), exist_ok=True)
+        depth = sphere_depth(p, width, height, focal, focal, width / 2.0, height / 2.0, sphere_radius)
+        depth = depth + np.where(depth > 0, rng.normal(0.0, 1e-3, depth.shape), 0.0).astype(np.float32)
+        mask = (depth > 0) & (rng.uniform(size=depth.shape) > 0.002)
+        occ = rng.uniform(size=depth.shape) > 0.05
+        Image.fromarray(np.roll(base, 7 * i, axis=1)).save(os.path.join(d, "left.png"), compress_level=1)
+        np.save(os.path.join(d, f"out_{model_name}", "depth.npy"), depth.astype(np.float32))
+        np.save(os.path.join(d, "left_mask.npy"), mask)
+        np.save(os.path.join(d, f"out_{model_name}", "occlusion_mask.npy"), occ)
+    return scene

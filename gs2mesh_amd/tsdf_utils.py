@@ -10,16 +10,28 @@ the host (scipy.ndimage; cv2 is not a dependency).  Frames can come from disk (`
 ``out_<model>/depth.npy``, ...: the reference layout, so ``--skip_rendering`` style resumes work) or
 from memory via ``frame_source`` (the in-memory hand-off).
 
+``TSDF(..., fuse="batch")`` (or ``args.TSDF_fuse = "batch"``) fuses the same frames into the same volume (every block, every
+voxel bit for bit) in sweeps of at most ``MAX_SWEEP`` frames: a thread pool reads the next sweep from disk while the current one is integrated,
+the masks of a sweep are preprocessed on the device in one call (``mask_preprocess``, ``gs2m_mask_preprocess``), the sweep
+is one ``integrate_batch`` and the vertex normals are computed on the device.  The mesh is the same mesh; its vertex and
+triangle ORDER follows the volume's block slots, which atomics hand out in either path (two runs of one path differ in it
+too), so meshes compare by their cut-edge keys (``mesh.edge_index``), and the vertex normals, summed in triangle order, agree
+to rounding (each equals the host statement on its own mesh bit for bit).  The default, ``fuse="frame"``, is the loop above.
+
 After ``run()``: ``self.volume`` (gs2mesh_amd.integration.ScalableTSDFVolume) and ``self.mesh`` (marching
 cubes on the GPU, ``gs2m_tsdf_extract``); ``save_mesh`` / ``clean_mesh`` write the reference's
 ``<out_name>_mesh.ply`` / ``<out_name>_cleaned_mesh.ply`` (tsdf_utils.py:112-142).
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
+import time
+from concurrent.futures import Future, ThreadPoolExecutor
 
 import numpy as np
 
+from . import _lib
 from .integration import (Image, PinholeCameraIntrinsic, RGBDImage, ScalableTSDFVolume,
                           TSDFVolumeColorType)
 
@@ -51,8 +63,70 @@ def preprocess_object_mask(mask, invert=False, erode=True, closing_kernel_size=1
     return m
 
 
+def _u8_mask(m):
+    """a mask (host array or tensor of any dtype, non-zero = true) as the u8 the kernel reads (non-zero = true): bool and
+    uint8 masks as they are"""
+    if hasattr(m, "is_cuda"):                     # torch tensor
+        import torch
+        return m if m.dtype in (torch.uint8, torch.bool) else m != 0
+    m = np.asarray(m)
+    if m.dtype == np.bool_:
+        return m.view(np.uint8)
+    return m if m.dtype == np.uint8 else (m != 0).view(np.uint8)
+
+
+def mask_preprocess(object_masks, occlusion_masks=None, invert=False, erode=True, closing_kernel_size=10,
+                    erosion_kernel_size=10, lib=None, device=0):
+    """``gs2m_mask_preprocess``: for every frame, ``preprocess_object_mask(object_mask, invert, erode, closing, erosion) &
+    occlusion_mask`` as a device u8 mask (0 / 1), all frames in one call.  ``object_masks`` / ``occlusion_masks``: lists of
+    [H,W] host arrays or device tensors (non-zero = true), or None; an entry (or a whole list) of None is an absent mask.
+    Returns the list of device masks (views of one [n,H,W] buffer), None where a frame has neither mask.  Runs on torch's
+    current stream: the uploads and the scratch this call drops are released in that stream's order."""
+    if object_masks is None and occlusion_masks is None:
+        raise ValueError("mask_preprocess: no masks")
+    n = len(object_masks) if object_masks is not None else len(occlusion_masks)
+    objs = list(object_masks) if object_masks is not None else [None] * n
+    occs = list(occlusion_masks) if occlusion_masks is not None else [None] * n
+    if len(objs) != n or len(occs) != n:
+        raise ValueError("mask_preprocess: object_masks and occlusion_masks must have the same length")
+    k1, k2 = int(closing_kernel_size), int(erosion_kernel_size)
+    if erode and (k1 < 1 or k2 < 1):
+        raise ValueError(f"mask_preprocess: kernel sizes must be >= 1 (closing {k1}, erosion {k2})")
+    shapes = {tuple(m.shape) for m in objs + occs if m is not None}
+    if not shapes:
+        return [None] * n
+    if len(shapes) != 1 or len(next(iter(shapes))) != 2:
+        raise ValueError(f"mask_preprocess: the masks must share one [H,W] shape, got {sorted(shapes)}")
+    H, W = next(iter(shapes))
+    import torch
+    lib = lib if lib is not None else _lib.get()
+    mem = _lib.MEMORY
+    obj_p, occ_p, out_p = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
+    with_mask = [objs[i] is not None or occs[i] is not None for i in range(n)]
+    # the kernel writes every pixel of every output: no fill
+    out_all = mem.empty((sum(with_mask), H, W), np.uint8, device)
+    keep, outs = [], []
+    for i in range(n):
+        o = mem.upload(_u8_mask(objs[i]), torch.uint8, device) if objs[i] is not None else None
+        c = mem.upload(_u8_mask(occs[i]), torch.uint8, device) if occs[i] is not None else None
+        out = out_all[len([x for x in outs if x is not None])] if with_mask[i] else None
+        keep += [o, c]
+        outs.append(out)
+        obj_p[i], occ_p[i], out_p[i] = mem.ptr(o), mem.ptr(c), mem.ptr(out)
+    morph = bool(erode) and any(o is not None for o in objs)
+    # every scratch word is written before it is read
+    scratch = mem.empty((2 * n * H * ((W + 63) // 64),), np.int64, device) if morph else None
+    st = mem.current_stream(device)
+    _lib.check(lib.gs2m_mask_preprocess(n, W, H, obj_p, occ_p, int(bool(invert)), int(bool(erode)), max(k1, 1), max(k2, 1), out_p,
+                                        mem.ptr(scratch), st), lib)
+    return outs
+
+
 class TSDF:
-    def __init__(self, renderer, stereo, args, out_name, frame_source=None, max_blocks=None, lib=None):
+    MAX_SWEEP = 32          # frames per integrate_batch sweep of fuse="batch" (equal sweeps of at most this many)
+    LOADER_THREADS = 8      # disk readers of fuse="batch" (capped by the CPUs this process may use)
+
+    def __init__(self, renderer, stereo, args, out_name, frame_source=None, max_blocks=None, lib=None, fuse=None):
         self.model_name = stereo.model_name if stereo is not None else getattr(args, "stereo_model", "DLNR_Middlebury")
         self.renderer = renderer
         self.out_name = out_name
@@ -62,6 +136,10 @@ class TSDF:
         self._lib = lib                       # None = the HIP library (tests inject the emulator build)
         self.volume = None
         self.mesh = None
+        self.fuse = fuse if fuse is not None else getattr(args, "TSDF_fuse", "frame")
+        if self.fuse not in ("frame", "batch"):
+            raise ValueError(f"fuse must be 'frame' or 'batch', got {self.fuse!r}")
+        self.timings = {}       # wall seconds per stage of the last run(): fuse, extract, normals (+ load_wait, mask, integrate: batch)
 
     def _load_frame(self, camera_number):
         if self.frame_source is not None:
@@ -77,11 +155,51 @@ class TSDF:
             fr["occlusion"] = np.load(os.path.join(d, f'out_{self.model_name}', 'occlusion_mask.npy')).astype(bool)
         return fr
 
-    def run(self, visualize=False):
+    def _selected(self):
+        """camera numbers to fuse, in order (TSDF_dilate / TSDF_valid / TSDF_skip; tsdf_utils.py:60-66)"""
         a = self.args
         n = len(self.renderer)
         valid = a.TSDF_valid if a.TSDF_valid is not None else list(range(n))
         skip = a.TSDF_skip if a.TSDF_skip is not None else []
+        out = []
+        for camera_number, _ in enumerate(self.renderer.left_cameras):
+            if camera_number % a.TSDF_dilate != 0:
+                continue
+            if valid is not None and camera_number not in valid:
+                continue
+            if skip is not None and camera_number in skip:
+                continue
+            out.append(camera_number)
+        return out
+
+    def _intrinsic(self, camera_number):
+        c = self.renderer.left_cameras[camera_number]
+        return PinholeCameraIntrinsic(c['width'], c['height'], c['fx'], c['fy'], c['cx'], c['cy'])
+
+    def _world_to_camera(self, camera_number):
+        extrinsic = self.renderer.left_cameras[camera_number]['extrinsic'].copy()
+        extrinsic[:3, 3] /= self.args.TSDF_scale
+        return np.linalg.inv(extrinsic)
+
+    def _sweeps(self, cameras):
+        """consecutive cameras sharing one intrinsic, cut into equal sweeps of at most MAX_SWEEP (bench.py's rule)"""
+        groups = []
+        for c in cameras:
+            i = self._intrinsic(c)
+            key = (i.width, i.height, i.fx, i.fy, i.cx, i.cy)
+            if groups and groups[-1][0] == key:
+                groups[-1][1].append(c)
+            else:
+                groups.append((key, [c]))
+        sweeps = []
+        for _, g in groups:
+            size = -(-len(g) // -(-len(g) // int(self.MAX_SWEEP)))
+            sweeps += [g[i:i + size] for i in range(0, len(g), size)]
+        return sweeps
+
+    def run(self, visualize=False):
+        a = self.args
+        self._t_start = time.perf_counter()
         voxel_length = a.TSDF_voxel / 512
         kw = {} if self.max_blocks is None else dict(max_blocks=self.max_blocks)
         if self._lib is not None:
@@ -89,13 +207,10 @@ class TSDF:
         volume = ScalableTSDFVolume(voxel_length=float(voxel_length), sdf_trunc=a.TSDF_sdf_trunc,
                                     color_type=TSDFVolumeColorType.RGB8, **kw)
         baseline = self.renderer.baseline
-        for camera_number, left_camera in enumerate(self.renderer.left_cameras):
-            if camera_number % a.TSDF_dilate != 0:
-                continue
-            if valid is not None and camera_number not in valid:
-                continue
-            if skip is not None and camera_number in skip:
-                continue
+        if self.fuse == "batch":
+            self._fuse_batch(volume)
+            return self._finish(volume, on_device=True)
+        for camera_number in self._selected():
             fr = self._load_frame(camera_number)
             mask = None
             if a.TSDF_use_mask and fr.get("mask") is not None:
@@ -107,21 +222,83 @@ class TSDF:
                 mask = occ if mask is None else (np.asarray(mask).astype(bool) & occ)
             if mask is not None:
                 mask = np.asarray(mask).astype(np.uint8)
-            extrinsic = left_camera['extrinsic'].copy()
-            extrinsic[:3, 3] /= a.TSDF_scale
             depth_trunc = baseline * a.TSDF_max_depth_baselines / a.TSDF_scale
             rgbd = RGBDImage.create_from_color_and_depth(Image(fr["image"]), Image(fr["depth"]),
                                                          depth_scale=a.TSDF_scale, depth_trunc=depth_trunc,
                                                          convert_rgb_to_intensity=False)
-            intr = PinholeCameraIntrinsic(left_camera['width'], left_camera['height'], left_camera['fx'],
-                                          left_camera['fy'], left_camera['cx'], left_camera['cy'])
-            volume.integrate(rgbd, intr, np.linalg.inv(extrinsic), mask=mask,
+            volume.integrate(rgbd, self._intrinsic(camera_number), self._world_to_camera(camera_number), mask=mask,
                              min_depth=a.TSDF_min_depth_baselines * baseline)
+        self._finish(volume, on_device=False)
+
+    def _finish(self, volume, on_device):
+        a = self.args
         volume.status()
+        t0 = time.perf_counter()
+        self.timings["fuse"] = t0 - self._t_start           # selection, loading and integration, up to the last voxel written
         self.volume = volume
         self.mesh = volume.extract_triangle_mesh()                  # tsdf_utils.py:108
         self.mesh.scale(a.TSDF_scale, (0, 0, 0))                    # :109
-        self.mesh.compute_vertex_normals()                          # :110
+        t1 = time.perf_counter()
+        if on_device:
+            self.mesh.compute_vertex_normals(on_device=True, lib=volume._lib, device=volume.device)
+        else:
+            self.mesh.compute_vertex_normals()                      # :110
+        t2 = time.perf_counter()
+        self.timings.update(extract=t1 - t0, normals=t2 - t1)
+
+    def _fuse_batch(self, volume):
+        """fuse="batch": the frames of ``_selected()`` in order, sweep by sweep.  Disk frames are read by a thread pool one sweep
+        ahead (at most two sweeps of frames are held); ``frame_source`` frames are fetched on this thread."""
+        sweeps = self._sweeps(self._selected())
+        tm = self.timings = dict(load_wait=0.0, mask=0.0, integrate=0.0)
+        pool = None
+        if self.frame_source is None and sweeps:
+            workers = max(1, min(int(self.LOADER_THREADS), len(os.sched_getaffinity(0))))
+            pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="tsdf-load")
+
+        def submit(cams):
+            if pool is None:
+                return [self._load_frame(c) for c in cams]
+            return [pool.submit(self._load_frame, c) for c in cams]
+
+        try:
+            pending = submit(sweeps[0]) if sweeps else []
+            for i, cams in enumerate(sweeps):
+                t0 = time.perf_counter()
+                frames = [f.result() if isinstance(f, Future) else f for f in pending]
+                pending = submit(sweeps[i + 1]) if i + 1 < len(sweeps) else []
+                tm["load_wait"] += time.perf_counter() - t0
+                self._integrate_sweep(volume, cams, frames)
+                del frames
+        finally:
+            if pool is not None:
+                pool.shutdown(wait=True, cancel_futures=True)
+
+    def _integrate_sweep(self, volume, cams, frames):
+        """one gs2m_mask_preprocess + one integrate_batch for the frames of one sweep (one intrinsic)"""
+        a = self.args
+        baseline = self.renderer.baseline
+        depth_trunc = baseline * a.TSDF_max_depth_baselines / a.TSDF_scale
+        intr = self._intrinsic(cams[0])
+        images, objs, occs = [], [], []
+        for fr in frames:
+            images.append(RGBDImage.create_from_color_and_depth(Image(fr["image"]), Image(fr["depth"]),
+                                                                depth_scale=a.TSDF_scale, depth_trunc=depth_trunc,
+                                                                convert_rgb_to_intensity=False))
+            objs.append(fr.get("mask") if a.TSDF_use_mask else None)
+            occs.append(fr.get("occlusion") if a.TSDF_use_occlusion_mask else None)
+        t0 = time.perf_counter()
+        masks = None
+        if any(m is not None for m in objs + occs):
+            if any(tuple(m.shape) != (intr.height, intr.width) for m in objs + occs if m is not None):
+                raise RuntimeError("[ScalableTSDFVolume::Integrate] Unsupported image format.")
+            masks = mask_preprocess(objs, occs, a.TSDF_invert_mask, a.TSDF_erode_mask, a.TSDF_closing_kernel_size,
+                                    a.TSDF_erosion_kernel_size, lib=volume._lib, device=volume.device)
+        t1 = time.perf_counter()
+        volume.integrate_batch(images, intr, [self._world_to_camera(c) for c in cams], masks=masks,
+                               min_depth=a.TSDF_min_depth_baselines * baseline)
+        self.timings["mask"] += t1 - t0
+        self.timings["integrate"] += time.perf_counter() - t1
 
     def save_mesh(self):
         """tsdf_utils.py:112-120."""

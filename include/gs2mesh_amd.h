@@ -474,6 +474,18 @@ int gs2m_tsdf_extract_mesh(gs2m_tsdf* t, gs2m_stream stream, int64_t* n_vertices
 int gs2m_tsdf_mesh_copy(gs2m_tsdf* t, gs2m_stream stream, double* vertices, double* colors, int32_t* edge_index, int32_t* triangles);
 int gs2m_mesh_cluster(int device, gs2m_stream stream, int64_t n_triangles, const int32_t* triangles, int32_t* labels,
                       int64_t* cluster_n_triangles, int64_t* n_clusters);
+/*
+ *   gs2m_mesh_vertex_normals TriangleMesh::ComputeVertexNormals (tsdf_utils.py:110), bit-identical to the numpy statement of
+ *                            gs2mesh_amd.mesh.TriangleMesh.compute_vertex_normals: triangle normal = np.cross(v1 - v0, v2 - v0)
+ *                            divided by its norm sqrt((x*x + y*y) + z*z) (by 1 when that is 0); vertex normal = the sum, from
+ *                            0.0, of the normals of the triangles that use it in np.add.at order (corner 0 of every triangle in
+ *                            ascending triangle order, then corner 1, then corner 2), normalised the same way (0 without
+ *                            triangles).  vertices [n_vertices][3] f64, triangles [n_triangles][3] i32, triangle_normals
+ *                            [n_triangles][3] f64 and vertex_normals [n_vertices][3] f64 are DEVICE pointers.  A vertex index
+ *                            outside 0..n_vertices-1 is an error.  Synchronises `stream` before it returns.
+ */
+int gs2m_mesh_vertex_normals(int device, gs2m_stream stream, int64_t n_vertices, const double* vertices, int64_t n_triangles,
+                             const int32_t* triangles, double* triangle_normals, double* vertex_normals);
 
 /* ------------------------------------------------------------------------------------ */
 /* stereo post-processing (between the stereo network and the TSDF)                     */
@@ -490,6 +502,27 @@ int gs2m_mesh_cluster(int device, gs2m_stream stream, int64_t n_triangles, const
 int gs2m_stereo_depth_occlusion(const float* disp_lr, const float* disp_rl, int width, int height,
                                 double fx_times_baseline, double occlusion_threshold, float* depth_out,
                                 uint8_t* mask_out, gs2m_stream stream);
+
+/*
+ * Replaces the object-mask preprocessing of TSDF.run (gs2mesh_utils/tsdf_utils.py:69-83) for n frames in one call.  Per frame:
+ *   m = object_mask != 0, inverted if invert != 0;
+ *   if erode != 0: m = erode_k2(close_k1(m)) -- cv2.MORPH_CLOSE with a closing_k x closing_k box of ones, then cv2.erode with an
+ *                  erosion_k x erosion_k box; default anchor (window [x - k/2, x + k - 1 - k/2] in both axes) and default
+ *                  border (every operation sees 1 outside the image when it erodes, 0 when it dilates);
+ *   out = m & (occlusion_mask != 0), written as 0 / 1 bytes.
+ * Bit-identical to gs2mesh_amd.tsdf_utils.preprocess_object_mask followed by the AND.  Any k >= 1 (also k > width or height);
+ * k < 1 is an error.
+ *   object_masks, occlusion_masks   host arrays [n] of [height][width] u8 DEVICE pointers (non-zero = true); either array or
+ *                                   any entry may be NULL (that mask is absent: an absent object mask counts as all true)
+ *   out_masks                       host array [n] of [height][width] u8 DEVICE pointers; entry i is written when frame i has
+ *                                   an object or an occlusion mask, and may be NULL (not touched) when it has neither
+ *   scratch                         DEVICE, 2 * n * height * ceil(width / 64) words; may be NULL when erode == 0 or no frame
+ *                                   has an object mask
+ * Asynchronous on `stream`.
+ */
+int gs2m_mask_preprocess(int n, int width, int height, const uint8_t* const* object_masks, const uint8_t* const* occlusion_masks,
+                         int invert, int erode, int closing_k, int erosion_k, uint8_t* const* out_masks, uint64_t* scratch,
+                         gs2m_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* PNG encoder (the Renderer's left.png / right.png)               */
