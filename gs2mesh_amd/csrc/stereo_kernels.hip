@@ -16,6 +16,7 @@
 #include "../../include/gs2mesh_amd.h"
 #include "platform.h"
 #include "mask_kernels.h"
+#include "sgm_kernels.h"
 
 void gs2m_set_error(const char* fmt, ...);
 
@@ -90,5 +91,47 @@ extern "C" int gs2m_mask_preprocess(int n, int width, int height, const uint8_t*
         unsigned long long* b_bits = a_bits ? a_bits + (size_t)nf * frame_words : nullptr;
         gs2m_launch_mask_preprocess((hipStream_t)stream, B, nf, width, height, invert, erode, closing_k, erosion_k, a_bits, b_bits);
     }
+    return 0;
+}
+
+extern "C" int64_t gs2m_stereo_sgm_scratch_bytes(int width, int height, int max_disparity) {
+    if (width <= 0 || height <= 0 || height > 65535 || (int64_t)width * height > 0x7fffffffll || max_disparity < 64 ||
+        max_disparity > 64 * SGM_MAX_K || max_disparity % 64 != 0)
+        return -1;
+    return sgm_scratch_layout(nullptr, width, height, max_disparity).bytes;
+}
+
+extern "C" int gs2m_stereo_sgm(const uint8_t* left_rgb8, const uint8_t* right_rgb8, int width, int height, int max_disparity,
+                               int p1, int p2, float* disp_lr, float* disp_rl, void* scratch, int64_t scratch_bytes,
+                               uint16_t* tap_cost_lr, gs2m_stream stream) {
+    if (!left_rgb8 || !right_rgb8) {
+        gs2m_set_error("gs2m_stereo_sgm: NULL image");
+        return 1;
+    }
+    if (max_disparity < 64 || max_disparity > 64 * SGM_MAX_K || max_disparity % 64 != 0) {
+        gs2m_set_error("gs2m_stereo_sgm: max_disparity must be a multiple of 64 in [64, %d], got %d", 64 * SGM_MAX_K, max_disparity);
+        return 1;
+    }
+    const int64_t need = gs2m_stereo_sgm_scratch_bytes(width, height, max_disparity);
+    if (need < 0) {
+        gs2m_set_error("gs2m_stereo_sgm: unsupported image size %d x %d", width, height);
+        return 1;
+    }
+    if (p1 <= 0 || p1 > p2 || p2 > 190) {
+        gs2m_set_error("gs2m_stereo_sgm: penalties must satisfy 0 < p1 <= p2 <= 190, got p1 = %d, p2 = %d", p1, p2);
+        return 1;
+    }
+    if (!scratch || scratch_bytes < need) {
+        gs2m_set_error("gs2m_stereo_sgm: scratch of %lld bytes, gs2m_stereo_sgm_scratch_bytes asks for %lld",
+                       (long long)(scratch ? scratch_bytes : 0), (long long)need);
+        return 1;
+    }
+    if (((uintptr_t)scratch | (uintptr_t)tap_cost_lr) & 15u) {
+        gs2m_set_error("gs2m_stereo_sgm: scratch and tap_cost_lr must be 16-byte aligned");
+        return 1;
+    }
+    if (!disp_lr && !disp_rl && !tap_cost_lr) return 0;
+    sgm_launch((hipStream_t)stream, left_rgb8, right_rgb8, width, height, max_disparity, p1, p2, disp_lr, disp_rl,
+               sgm_scratch_layout(scratch, width, height, max_disparity), tap_cost_lr);
     return 0;
 }

@@ -272,7 +272,27 @@ class Renderer:
         if wait:
             self._writer.flush()
 
+    def write_pair(self, camera_number, rgb8, wait=True):
+        """left.png / right.png of view `camera_number` from an already rendered pair (``render_pair_device(...)["rgb8"]``, or
+        its host copy): the files ``render_image_pair`` would write, without rendering again.  With png_encoder="device"
+        the pair is encoded on the GPU and written by the writer thread (``wait=False`` returns once that is enqueued,
+        ``flush()`` waits); the PIL path writes before it returns."""
+        out_dir = self._out_dir(camera_number)
+        paths = [os.path.join(out_dir, f'{name}.png') for name in ('left', 'right')]
+        if self.png_encoder == "device" and isinstance(rgb8, torch.Tensor) and rgb8.is_cuda:
+            if self._writer is None:
+                from .png import PngWriter
+                self._writer = PngWriter(self._encoder())
+            self._writer.submit(paths, rgb8)
+            if wait:
+                self._writer.flush()
+            return
+        from PIL import Image as PILImage
+        host = rgb8.cpu().numpy() if isinstance(rgb8, torch.Tensor) else np.asarray(rgb8)
+        for k, path in enumerate(paths):
+            PILImage.fromarray(host[k], mode="RGB").save(path)
+
     def flush(self):
-        """Wait until every file ``render_image_pairs`` enqueued is on disk (re-raises a write error)."""
+        """Wait until every file ``render_image_pairs`` / ``write_pair`` enqueued is on disk (re-raises a write error)."""
         if self._writer is not None:
             self._writer.flush()

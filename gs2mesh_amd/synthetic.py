@@ -238,3 +238,44 @@ def write_tsdf_scene(root, n_views, width, height, focal, seed, model_name="DLNR
         np.save(os.path.join(d, "left_mask.npy"), mask)
         np.save(os.path.join(d, f"out_{model_name}", "occlusion_mask.npy"), occ)
     return scene
+
+
+def random_dot_stereogram(width=176, height=120, seed=0):
+    """A stereo pair with a known disparity for the matcher's tests: (left, right, true_disparity).  ``left`` / ``right`` are
+    [H,W,3] u8 with equal channels (so the matcher's grey value is the channel value), ``true_disparity`` [H,W] f64 is the
+    left image's: a disc of radius 0.375 H in the centre bulging from 14 px at its rim to 22 px, over a 5 px background.
+    The left image is lightly smoothed noise; the right eye is its z-buffered forward warp (nearest pixel wins), holes
+    filled with fresh noise."""
+    rng = np.random.default_rng(seed)
+    H, W = int(height), int(width)
+    yy, xx = np.mgrid[:H, :W]
+    r2 = ((xx - W / 2) ** 2 + (yy - H / 2) ** 2) / (0.375 * H) ** 2
+    dtrue = np.where(r2 < 1, 14.0 + 8.0 * np.sqrt(np.clip(1 - r2, 0, 1)), 5.0)
+    left = rng.integers(0, 256, (H, W)).astype(np.int32)
+    left = (left + np.roll(left, 1, 0) + np.roll(left, 1, 1) + np.roll(left, (1, 1), (0, 1))) // 4
+    right = rng.integers(0, 256, (H, W)).astype(np.int32)
+    shift = np.rint(dtrue).astype(np.int64)
+    xr = xx - shift
+    order = np.argsort(dtrue, axis=None, kind="stable")          # far to near: the nearest source is written last
+    oy, ox = np.unravel_index(order, (H, W))
+    ok = (xr[oy, ox] >= 0) & (xr[oy, ox] < W)
+    right[oy[ok], xr[oy, ox][ok]] = left[oy[ok], ox[ok]]
+    to_rgb = lambda g: np.ascontiguousarray(np.repeat(g.astype(np.uint8)[:, :, None], 3, axis=2))
+    return to_rgb(left), to_rgb(right), dtrue
+
+
+def textured_sphere(P, seed, radius=0.6, sigma=0.02):
+    """Gaussians (GaussianModel layout, like ``synth_v1``) of a matchable surface: P opaque isotropic splats of scale
+    ``sigma`` with random DC colours on the sphere of ``radius`` around the origin, zero rest SH (the same colour from
+    every direction, as stereo assumes)."""
+    rng = np.random.default_rng(seed)
+    d = rng.normal(size=(P, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    xyz = (d * radius).astype(np.float32)
+    scaling = np.full((P, 3), np.log(sigma), np.float32)
+    rotation = np.tile(np.array([1, 0, 0, 0], np.float32), (P, 1))
+    o = np.full((P, 1), 0.95)
+    opacity = np.log(o / (1 - o)).astype(np.float32)
+    f_dc = RGB2SH(rng.uniform(0, 1, size=(P, 1, 3))).astype(np.float32)
+    return dict(xyz=xyz, features_dc=f_dc, features_rest=np.zeros((P, 15, 3), np.float32), scaling=scaling,
+                rotation=rotation, opacity=opacity)

@@ -35,7 +35,8 @@ extern "C" {
                             (gs2m_tsdf_block_map / _map_keys / _map_bytes / _replace / _extract_mesh / _mesh_copy,
                             gs2m_mesh_cluster, gs2m_raster_blend_cycles, GS2M_OPT_BLEND_MODE / _PROFILE) + round 6
                             (gs2m_tsdf_flags_device, GS2M_OPT_BIN_LANE_TILES, GS2M_OPT_PROJECT_SHARED_READ, GS2M_OPT_EXACT_TILE_CULL level 2; GS2M_OPT_BLEND_MODE 1
-                            removed).  The Python binding checks it at load time */
+                            removed).  Added since without a new number: gs2m_stereo_sgm / gs2m_stereo_sgm_scratch_bytes.  The Python binding checks it at
+                            load time */
 
 typedef void* gs2m_stream; /* hipStream_t */
 
@@ -523,6 +524,36 @@ int gs2m_stereo_depth_occlusion(const float* disp_lr, const float* disp_rl, int 
 int gs2m_mask_preprocess(int n, int width, int height, const uint8_t* const* object_masks, const uint8_t* const* occlusion_masks,
                          int invert, int erode, int closing_k, int erosion_k, uint8_t* const* out_masks, uint64_t* scratch,
                          gs2m_stream stream);
+
+/*
+ * The built-in stereo matcher of gs2mesh_amd.stereo_utils.Stereo (stereo_model "SGM"): semi-global matching over four paths
+ * on a 9 x 7 census transform.  It stands where the reference runs its stereo network (stereo_utils.py:105-124) and makes no
+ * claim to that network's quality; it needs no weights.  Integer arithmetic up to the last step, so the output is defined
+ * bit for bit:
+ *   1. grey      g = (77 R + 150 G + 29 B + 128) >> 8
+ *   2. census    9 wide x 7 high around the pixel without the centre (62 bits): bit = g(neighbour) < g(centre); neighbours
+ *                outside the image take the nearest pixel inside
+ *   3. cost      left-based pass, d in [0, D): C(y,x,d) = popcount(census_L(y,x) xor census_R(y,x-d)), 62 where x - d < 0
+ *   4. paths     r in {right, left, down, up}: L_r = C on the first pixel of a path; after it, with p' the previous pixel and
+ *                m = min_k L_r(p',k):  L_r(p,d) = C(p,d) + min(L_r(p',d), L_r(p',d-1) + p1, L_r(p',d+1) + p1, m + p2) - m
+ *                (the d-1 / d+1 terms are absent outside [0, D));  S = sum of the four L_r
+ *   5. winner    d* = argmin_d S, the lowest d on ties
+ *   6. sub-pixel in f32: sm = S(d*-1), sp = S(d*+1), s0 = S(d*), den = sm + sp - 2 s0; if 0 < d* < D-1 and den > 0:
+ *                disp = d* + (sm - sp) / (2 den), else disp = d*.  Every pixel gets a value in [0, D-1].
+ *   7. disp_rl   the right-based pass (candidate x + d in the left image, cost 62 where x + d >= W): the numbers the reference's
+ *                protocol gives, i.e. the left-based matcher on (flip_x(right), flip_x(left)) flipped back.
+ *   left_rgb8, right_rgb8   [H][W][3] u8 device (one eye of gs2m_render_views' rgb8)
+ *   max_disparity           D: a multiple of 64 in [64, 1024]
+ *   p1, p2                  0 < p1 <= p2 <= 190 (a path cost then fits 8 bits)
+ *   disp_lr, disp_rl        [H][W] f32 device; either may be NULL (both NULL and no tap: nothing is done)
+ *   scratch, scratch_bytes  device, 16-byte aligned, at least gs2m_stereo_sgm_scratch_bytes (-1 for sizes it refuses); the two
+ *                           passes share it
+ *   tap_cost_lr             NULL, or [H][W][D] u16 device, 16-byte aligned: S of the left-based pass (tests)
+ * Asynchronous on `stream`; bad arguments return 1 with gs2m_last_error().
+ */
+int64_t gs2m_stereo_sgm_scratch_bytes(int width, int height, int max_disparity);
+int gs2m_stereo_sgm(const uint8_t* left_rgb8, const uint8_t* right_rgb8, int width, int height, int max_disparity, int p1, int p2,
+                    float* disp_lr, float* disp_rl, void* scratch, int64_t scratch_bytes, uint16_t* tap_cost_lr, gs2m_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* PNG encoder (the Renderer's left.png / right.png)               */
