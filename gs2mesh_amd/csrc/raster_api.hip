@@ -91,6 +91,17 @@ struct gs2m_raster {
     ViewStatus* d_status = nullptr;  // slot 0: the sticky word (device atomics)
     ViewStatus* h_status = nullptr;  // pinned, device-mapped: slots 1.. are WRITTEN BY k_tile_scan itself (round 4: no status copy
                                      // launch behind every pass); slot 0 mirrors the sticky word at gs2m_raster_status
+    // backward pass (gs2m_rasterize_backward): grow-only arenas, and what the last call left in the forward state
+    float* d_bw_rows = nullptr;          // [rows][GS2M_BW_ROW] one row per (Gaussian, tile of its rect)
+    size_t bw_rows_cap = 0;              // floats
+    unsigned* d_bw_offset = nullptr;     // [P] first row of every Gaussian
+    size_t bw_offset_cap = 0;
+    unsigned* d_bw_blocks = nullptr;     // [ceil(P / 256)] scan scratch
+    size_t bw_blocks_cap = 0;
+    unsigned long long* d_bw_total = nullptr;
+    unsigned long long bw_last_rows = 0;  // instance rows of the last backward call
+    bool fw_valid = false;               // the state is that of ONE gs2m_rasterize_forward call
+    int fw_P = 0, fw_W = 0, fw_H = 0, fw_tile_rows = 1;
     // last call
     int last_P = 0, last_nv = 0, last_tiles = 0, last_views_total = 0;
     unsigned last_cap = 0;
@@ -151,6 +162,10 @@ extern "C" int gs2m_raster_destroy(gs2m_raster* r) {
     (void)hipFree(r->d_tmp);
     (void)hipFree(r->d_status);
     (void)hipFree(r->d_blend_prof);
+    (void)hipFree(r->d_bw_rows);
+    (void)hipFree(r->d_bw_offset);
+    (void)hipFree(r->d_bw_blocks);
+    (void)hipFree(r->d_bw_total);
     (void)hipHostFree(r->h_status);
     for (auto& p : r->ev_live) {
         (void)hipEventDestroy(p.a);
@@ -272,6 +287,9 @@ extern "C" int gs2m_raster_reserve(gs2m_raster* r, int P, int n_views, int W, in
         return 1;
     }
     HIPCHK(hipSetDevice(r->device));
+    // growing an arena frees the projected records / lists / ranges a later gs2m_rasterize_backward would read: whoever calls
+    // this ends the forward state (gs2m_rasterize_forward sets it again once its own pass, reserve included, has been launched)
+    r->fw_valid = false;
     const int nv = n_views < GS2M_MAX_PASS_VIEWS ? (n_views < 1 ? 1 : n_views) : GS2M_MAX_PASS_VIEWS;
     const int tiles = ((W + GS2M_TILE - 1) / GS2M_TILE) * ((H + GS2M_TILE - 1) / GS2M_TILE);
     int chunk, n_wg;
@@ -479,12 +497,18 @@ extern "C" int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const
         return 1;
     }
     r->last_views_total = 1;
+    r->fw_valid = false;
     if (P == 0) {
         // rasterize_points.cu:68,81: the zero-filled image is returned untouched
         HIPCHK(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * (size_t)width * height, st));
         HIPCHK(hipMemsetAsync(r->h_status + 1, 0, sizeof(ViewStatus), st));   // stream-ordered like a pass's own status write
         r->last_P = 0;
         r->last_nv = 1;
+        r->fw_valid = true;
+        r->fw_P = 0;
+        r->fw_W = width;
+        r->fw_H = height;
+        r->fw_tile_rows = r->opt_tile_rows;
         return 0;
     }
     if (!means3D || !opacities || !background || !viewmatrix || !projmatrix || !cam_pos) {
@@ -527,6 +551,147 @@ extern "C" int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const
     int rc = run_views(r, g, 1, 1, width, height, out_color, nullptr, radii, 0, st, nullptr);
     r->opt_debug = saved_debug;
     if (rc) return rc;
+    r->fw_valid = true;
+    r->fw_P = P;
+    r->fw_W = width;
+    r->fw_H = height;
+    r->fw_tile_rows = r->opt_tile_rows;
+    return 0;
+}
+
+// Backward of the last gs2m_rasterize_forward on this handle: the projected records, the sorted per-tile lists and the ranges
+// are still in the arenas.  Stages: row offsets (scan of the rect areas) -> clear the row buffer -> compositing backward (one row
+// per instance, plain stores) -> per-Gaussian backward (sums the rows, continues to the inputs).
+extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int R, const float* background, int width,
+                                       int height, const float* means3D, const float* shs, const float* colors_precomp,
+                                       const float* scales, float scale_modifier, const float* rotations,
+                                       const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                       const float* cam_pos, float tan_fovx, float tan_fovy, const float* dL_dpix,
+                                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                       int debug, gs2m_stream stream) {
+    (void)R;   // the instance count is part of the handle's state
+    if (!r) {
+        gs2m_set_error("null handle");
+        return 1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(r->device));
+    if (!r->fw_valid) {
+        gs2m_set_error("gs2m_rasterize_backward: the handle holds no state of a gs2m_rasterize_forward call (the last call was "
+                       "gs2m_render_views or gs2m_raster_reserve, or none)");
+        return 1;
+    }
+    if (P != r->fw_P || width != r->fw_W || height != r->fw_H) {
+        gs2m_set_error("gs2m_rasterize_backward: P %d / %dx%d do not match the last forward (P %d / %dx%d)", P, width, height,
+                       r->fw_P, r->fw_W, r->fw_H);
+        return 1;
+    }
+    if (r->fw_tile_rows != 1 || r->opt_tile_rows != 1) {
+        gs2m_set_error("gs2m_rasterize_backward needs the 16 x 16 instance lists: GS2M_OPT_TILE_ROWS 2 is not supported");
+        return 1;
+    }
+    if (r->opt_pair_batch > 1) {
+        gs2m_set_error("gs2m_rasterize_backward is not available with GS2M_OPT_PAIR_BATCH (a gs2m_render_views option)");
+        return 1;
+    }
+    if (D < 0 || D > 3) {
+        gs2m_set_error("SH degree %d not in 0..3", D);
+        return 1;
+    }
+    if (P == 0) return 0;   // every output is empty
+    if (!dL_dpix || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot ||
+        !means3D || !background || !viewmatrix || !projmatrix || !cam_pos) {
+        gs2m_set_error("gs2m_rasterize_backward: NULL required pointer");
+        return 1;
+    }
+    if ((shs == nullptr) == (colors_precomp == nullptr)) {
+        gs2m_set_error("Please provide excatly one of either SHs or precomputed colors!");
+        return 1;
+    }
+    if (((scales == nullptr || rotations == nullptr) && cov3D_precomp == nullptr) ||
+        ((scales != nullptr || rotations != nullptr) && cov3D_precomp != nullptr)) {
+        gs2m_set_error("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
+        return 1;
+    }
+    if (shs && (M < (D + 1) * (D + 1) || !dL_dsh)) {
+        gs2m_set_error("gs2m_rasterize_backward: M = %d SH coefficients < (D+1)^2 = %d, or dL_dsh is NULL", M, (D + 1) * (D + 1));
+        return 1;
+    }
+    const int saved_debug = r->opt_debug;
+    if (debug) r->opt_debug = 1;
+    struct Restore {
+        gs2m_raster* r;
+        int v;
+        ~Restore() { r->opt_debug = v; }
+    } restore{r, saved_debug};
+    const int gx = (width + GS2M_TILE - 1) / GS2M_TILE, gy = (height + GS2M_TILE - 1) / GS2M_TILE;
+    const GeomRecs recs{r->d_recs, r->d_recs + 2 * (size_t)P};
+    if (ensure(&r->d_bw_offset, &r->bw_offset_cap, (size_t)P)) return 1;
+    if (ensure(&r->d_bw_blocks, &r->bw_blocks_cap, (size_t)(P + 255) / 256)) return 1;
+    if (!r->d_bw_total) HIPCHK(hipMalloc((void**)&r->d_bw_total, sizeof(unsigned long long)));
+    gs2m_launch_pack_camera(st, r->d_cams, 0, viewmatrix, projmatrix, cam_pos, background, tan_fovx, tan_fovy, width, height, 16);
+    gs2m_launch_bw_row_offsets(st, recs, P, r->d_bw_blocks, r->d_bw_offset, r->d_bw_total);
+    if (dbg_check(r, st, "backward row offsets")) return 1;
+    // the row count sizes the arena: one host round trip (the reference's forward reads num_rendered the same way)
+    unsigned long long n_rows = 0ull;
+    HIPCHK(hipMemcpyAsync(&n_rows, r->d_bw_total, sizeof(n_rows), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (r->h_status[1].overflow) {
+        gs2m_set_error("gs2m_rasterize_backward: the forward overflowed its instance arena (gs2m_raster_status / gs2m_raster_reserve, then run it again)");
+        return 1;
+    }
+    if (n_rows > 0xfffffff0ull) {
+        gs2m_set_error("gs2m_rasterize_backward: %llu instance rows exceed the 32-bit row offsets", n_rows);
+        return 1;
+    }
+    if (ensure(&r->d_bw_rows, &r->bw_rows_cap, (size_t)(n_rows ? n_rows : 1ull) * GS2M_BW_ROW)) return 1;
+    r->bw_last_rows = n_rows;
+    if (n_rows) {
+        // rows no wave writes (instances behind every pixel's last contributor, tiles a cull level dropped) must read as zero
+        HIPCHK(hipMemsetAsync(r->d_bw_rows, 0, sizeof(float) * (size_t)n_rows * GS2M_BW_ROW, st));
+        gs2m_launch_blend_backward(st, gx, gy, r->d_keys, r->d_tile_start, recs, r->d_cams, P, r->last_cap, dL_dpix, r->d_bw_offset,
+                                   r->d_bw_rows, n_rows);
+        if (dbg_check(r, st, "blend backward")) return 1;
+    }
+    GaussIn g;
+    g.xyz = means3D;
+    g.scales = scales;
+    g.rots = rotations;
+    g.opac = nullptr;
+    g.shs = shs;
+    g.shs_rest = nullptr;
+    g.shs_packed = nullptr;
+    g.cov3D_precomp = cov3D_precomp;
+    g.colors_precomp = colors_precomp;
+    g.ids = nullptr;
+    g.P = P;
+    g.D = D;
+    g.M = M;
+    g.raw = 0;
+    g.scale_modifier = scale_modifier;
+    BwOut o;
+    o.dL_dmean2D = dL_dmean2D;
+    o.dL_dconic = dL_dconic;
+    o.dL_dopacity = dL_dopacity;
+    o.dL_dcolor = dL_dcolor;
+    o.dL_dmean3D = dL_dmean3D;
+    o.dL_dcov3D = dL_dcov3D;
+    o.dL_dsh = shs ? dL_dsh : nullptr;
+    o.dL_dscale = dL_dscale;
+    o.dL_drot = dL_drot;
+    gs2m_launch_gaussian_backward(st, g, r->d_cams, recs, r->d_bw_offset, r->d_bw_rows, n_rows, o);
+    if (dbg_check(r, st, "gaussian backward")) return 1;
+    return 0;
+}
+
+extern "C" int gs2m_raster_backward_rows(gs2m_raster* r, int64_t* rows, int64_t* arena_bytes) {
+    if (!r) {
+        gs2m_set_error("null handle");
+        return 1;
+    }
+    if (rows) *rows = (int64_t)r->bw_last_rows;
+    if (arena_bytes) *arena_bytes = r->d_bw_rows ? (int64_t)(r->bw_rows_cap * sizeof(float)) : 0;
     return 0;
 }
 
@@ -566,6 +731,7 @@ extern "C" int gs2m_render_views(gs2m_raster* r, const gs2m_gaussians* gs, const
         return 1;
     }
     r->last_views_total = n_views;
+    r->fw_valid = false;   // the arenas now hold a multi-view pass: no gs2m_rasterize_backward on it
     const size_t img = (size_t)W * H;
     if (gs->P == 0) {
         if (out_color) HIPCHK(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * img * n_views, st));

@@ -1,0 +1,236 @@
+// raster_backward_blend.h -- backward of the per-tile compositing (the reference's backward renderCUDA, backward.cu:400-557).
+//
+// One wave per 16 x 16 tile, four pixels per lane laid out as the tile's four 8 x 8 quadrants (the decomposition of the forward's
+// variant 4, raster_blend.h).  The forward does not write final_T / n_contrib (raster_blend.h:8), so the wave walks the tile's
+// sorted list TWICE with one alpha function (bw_alpha):
+//   1. front to back: per pixel the transmittance after its last contributor (T_final) and the list position after that
+//      contributor (n_contrib) -- the three decisions of renderCUDA, including stop-before-accumulate;
+//   2. back to front from the wave's largest n_contrib: T is rebuilt by division (T / (1 - alpha), backward.cu:503), the colour
+//      behind a contributor is carried as the reference's accum_rec recurrence (:515), and every contributing pixel adds to the
+//      nine per-instance values  dL/dmean2D (2)  dL/dconic (3)  dL/dopacity (1)  dL/dcolour (3).
+// Both walks evaluate bw_alpha on the same staged record with explicit FMAs, so they take the same threshold decisions.
+//
+// Accumulation across tiles WITHOUT float atomics (DESIGN.md "Backward accumulation"): the reference adds every pixel's
+// contribution with atomicAdd (:523-554) -- 64 lanes into 64 different rows, the slowest shape global float atomics have on
+// this chip, and a sum whose rounding depends on arrival order.  Here a lane first adds its four pixels, the wave reduces the nine
+// values over its 64 lanes in registers (a transposing butterfly: 10 shuffles for eight of them, 6 for the ninth) and lanes 0..8
+// store ONE row of GS2M_BW_ROW floats per (Gaussian, tile) instance with plain stores, at
+//     row = offset[g] + (ty - y0) * (x1 - x0) + (tx - x0)       (the tile's slot inside the Gaussian's tile rect),
+// so the rows of a Gaussian are contiguous and the per-Gaussian pass (raster_backward_project.h) sums them in slot order: the
+// gradients are bitwise reproducible.  The reduction is skipped when no lane contributed; rows that are never written (instances
+// behind every pixel's last contributor, tiles an exact cull level removed from the rect) read as zero because the row buffer is
+// cleared before the launch.
+//
+// Departures of the reference's backward from the true derivative, reproduced here (they are the contract):
+//   * min(0.99, o G) is ignored in the derivative -- straight-through (backward.cu:499, :541): dL/dG = o dL/dalpha and
+//     dL/do = G dL/dalpha also where the cap binds;
+//   * dL/dmean2D is accumulated in NDC-scaled units, 0.5 W and 0.5 H (:460-461);
+//   * the background term  -T_final / (1 - alpha) * (bg . dL/dpixel)  (:531-534).
+#pragma once
+#include "raster_common.h"
+
+// alpha of one staged instance at one pixel: renderCUDA's `power`, G = exp(power), alpha = min(0.99, o G) and the two skip
+// decisions (forward.cu:331-343 = backward.cu:491-501).  Explicit FMAs: both walks of the kernel round alike.
+GS2M_DEVICE bool bw_alpha(const float4 A, const float4 B, const float pxf, const float pyf, float& dx, float& dy, float& G,
+                          float& alpha) {
+    dx = A.x - pxf;
+    dy = A.y - pyf;
+    const float power = fmaf(-0.5f * A.z * dx, dx, fmaf(-0.5f * B.x * dy, dy, -(A.w * dx) * dy));
+    G = gs2m_fast_exp(power);
+    alpha = fminf(0.99f, B.y * G);
+    return !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
+}
+
+// sum over the 64 lanes of eight per-lane values: afterwards lane l holds the complete sum of value 4 (l & 1) + 2 ((l >> 1) & 1) +
+// ((l >> 2) & 1).  Each step halves the values a lane carries (it keeps one half, sends the other to its partner): 4 + 2 + 1
+// shuffles, then 3 for the remaining lane bits.  The order of the additions is fixed by the lane number.
+GS2M_DEVICE float bw_reduce8(const float* a, const int lane) {
+    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4;
+    float b[4], c[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float recv = gs2m_shfl_xor(b0 ? a[k] : a[k + 4], 1);
+        b[k] = (b0 ? a[k + 4] : a[k]) + recv;
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float recv = gs2m_shfl_xor(b1 ? b[k] : b[k + 2], 2);
+        c[k] = (b1 ? b[k + 2] : b[k]) + recv;
+    }
+    float d = (b2 ? c[1] : c[0]) + gs2m_shfl_xor(b2 ? c[0] : c[1], 4);
+    d += gs2m_shfl_xor(d, 8);
+    d += gs2m_shfl_xor(d, 16);
+    d += gs2m_shfl_xor(d, 32);
+    return d;
+}
+GS2M_DEVICE float bw_reduce1(float d) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) d += gs2m_shfl_xor(d, m);
+    return d;
+}
+
+// grid: ceil(tiles / WPB) workgroups of WPB waves; wave w of workgroup b composites tile b * WPB + w of the (single) view.
+template <int WPB>
+GS2M_KERNEL void __launch_bounds__(64 * WPB)
+k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ tile_start, const GeomRecs recs,
+                 const CamUniform* __restrict__ cams, int P, unsigned cap, const float* __restrict__ dL_dpix,
+                 const unsigned* __restrict__ row_offset, float* __restrict__ rows, unsigned long long n_rows) {
+    // staged instance: a = {mx, my, ca, cb}, b = {cc, op, r, g}, c = {b, row index (bits)}
+    __shared__ float4 s_a[WPB][64], s_b[WPB][64];
+    __shared__ float2 s_c[WPB][64];
+    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
+    const CamUniform& cam = cams[0];
+    const int W = cam.W, H = cam.H, gx = cam.gx;
+    const int tiles = gx * cam.gy;
+    const int tile = gs2m_uniform((int)blockIdx.x * WPB + wave);
+    if (tile >= tiles) return;
+    const int ty = tile / gx, tx = tile - ty * gx;
+    float4* sa = &s_a[wave][0];
+    float4* sb = &s_b[wave][0];
+    float2* sc = &s_c[wave][0];
+    unsigned r0 = tile_start[tile], r1 = tile_start[tile + 1];
+    if (r0 > cap) r0 = cap;
+    if (r1 > cap) r1 = cap;
+    r0 = (unsigned)gs2m_uniform((int)r0);
+    r1 = (unsigned)gs2m_uniform((int)r1);
+    if (r1 <= r0) return;
+    const int px0 = tx * GS2M_TILE + (lane & 7), py0 = ty * GS2M_TILE + (lane >> 3);
+    const size_t plane = (size_t)H * W;
+    float pxf[4], pyf[4], T[4], dp0[4], dp1[4], dp2[4];
+    int ncontrib[4];     // list position (relative to r0) after the pixel's last contributor
+    bool done[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);
+        const bool inside = x < W && y < H;
+        pxf[k] = (float)x;
+        pyf[k] = (float)y;
+        T[k] = 1.0f;
+        ncontrib[k] = 0;
+        done[k] = !inside;
+        const size_t pix = (size_t)y * W + x;
+        dp0[k] = inside ? dL_dpix[pix] : 0.0f;
+        dp1[k] = inside ? dL_dpix[plane + pix] : 0.0f;
+        dp2[k] = inside ? dL_dpix[2 * plane + pix] : 0.0f;
+    }
+    // the 64 instances [base, base + 64) of the list -> LDS (lane l stages instance base + l)
+    auto stage = [&](const unsigned base) __attribute__((always_inline)) {
+        gs2m_wave_sync();   // the previous batch has been read by every lane
+        if (base + (unsigned)lane < r1) {
+            unsigned gid = (unsigned)(keys[base + lane] & 0xffffffffull);
+            const bool known = gid < (unsigned)P;   // never index the records with an id the forward cannot have written
+            gid = known ? gid : 0u;
+            const float4 ra = recs.ab[2 * (size_t)gid], rb = recs.ab[2 * (size_t)gid + 1], rc = recs.c[gid];
+            const unsigned rect0 = __float_as_uint(rc.z), rect1 = __float_as_uint(rc.w);
+            const int x0 = (int)(rect0 & 0xffffu), y0 = (int)(rect0 >> 16), x1 = (int)(rect1 & 0xffffu);
+            // slot of this tile inside the Gaussian's tile rect (the lists only hold tiles of the rect)
+            const unsigned row = row_offset[gid] + (unsigned)((ty - y0) * (x1 - x0) + (tx - x0));
+            sa[lane] = ra;
+            sb[lane] = rb;
+            if (!known) sb[lane].y = 0.0f;   // opacity 0: alpha < 1/255 everywhere, the instance is skipped by both walks
+            float2 c;
+            c.x = rc.x;
+            c.y = __uint_as_float(row);
+            sc[lane] = c;
+        }
+        gs2m_wave_sync();
+    };
+    // ---- walk 1, front to back: T_final and n_contrib of every pixel (forward.cu:324-357)
+    for (unsigned base = r0; base < r1; base += 64u) {
+        if (gs2m_ballot_b(!(done[0] && done[1] && done[2] && done[3])) == 0ull) break;
+        stage(base);
+        const int nb = (int)(r1 - base) < 64 ? (int)(r1 - base) : 64;
+        for (int j = 0; j < nb; ++j) {
+            const float4 A = sa[j], B = sb[j];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float dx, dy, G, alpha;
+                const bool ok = bw_alpha(A, B, pxf[k], pyf[k], dx, dy, G, alpha) && !done[k];
+                const float test_T = T[k] * (1.0f - alpha);
+                const bool sat = ok && test_T < 0.0001f;     // stop BEFORE accumulating (forward.cu:345-350)
+                done[k] = done[k] || sat;
+                if (ok && !sat) {
+                    T[k] = test_T;
+                    ncontrib[k] = (int)(base - r0) + j + 1;
+                }
+            }
+        }
+    }
+    int nmax = ncontrib[0] > ncontrib[1] ? ncontrib[0] : ncontrib[1];
+    nmax = nmax > ncontrib[2] ? nmax : ncontrib[2];
+    nmax = nmax > ncontrib[3] ? nmax : ncontrib[3];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const int o = gs2m_shfl_xor(nmax, m);
+        nmax = o > nmax ? o : nmax;
+    }
+    nmax = gs2m_uniform(nmax);
+    if (nmax == 0) return;
+    // ---- walk 2, back to front (backward.cu:464-556)
+    float Tf[4], bgdot[4], last_alpha[4], lc0[4], lc1[4], lc2[4], ar0[4], ar1[4], ar2[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        Tf[k] = T[k];
+        bgdot[k] = cam.bg[0] * dp0[k] + cam.bg[1] * dp1[k] + cam.bg[2] * dp2[k];
+        last_alpha[k] = 0.0f;
+        lc0[k] = lc1[k] = lc2[k] = 0.0f;
+        ar0[k] = ar1[k] = ar2[k] = 0.0f;
+    }
+    const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;   // pixel per NDC unit (backward.cu:460-461)
+    for (int bi = (nmax - 1) / 64; bi >= 0; --bi) {
+        const unsigned base = r0 + 64u * (unsigned)bi;
+        stage(base);
+        const int jtop = (nmax - 1 - 64 * bi) < 63 ? (nmax - 1 - 64 * bi) : 63;
+        for (int j = jtop; j >= 0; --j) {
+            const int idx = 64 * bi + j;
+            const float4 A = sa[j], B = sb[j];
+            const float2 Cc = sc[j];
+            float acc[8], acc8 = 0.0f;   // mx my ca cb cc op r g | b
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] = 0.0f;
+            bool any = false;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float dx, dy, G, alpha;
+                const bool ok = bw_alpha(A, B, pxf[k], pyf[k], dx, dy, G, alpha) && idx < ncontrib[k];
+                if (ok) {
+                    any = true;
+                    T[k] = T[k] / (1.0f - alpha);
+                    const float w = alpha * T[k];
+                    // colour composited behind this contributor (the reference's accum_rec recurrence, backward.cu:515)
+                    ar0[k] = last_alpha[k] * lc0[k] + (1.0f - last_alpha[k]) * ar0[k];
+                    ar1[k] = last_alpha[k] * lc1[k] + (1.0f - last_alpha[k]) * ar1[k];
+                    ar2[k] = last_alpha[k] * lc2[k] + (1.0f - last_alpha[k]) * ar2[k];
+                    lc0[k] = B.z;
+                    lc1[k] = B.w;
+                    lc2[k] = Cc.x;
+                    float dL_dalpha = (B.z - ar0[k]) * dp0[k] + (B.w - ar1[k]) * dp1[k] + (Cc.x - ar2[k]) * dp2[k];
+                    dL_dalpha *= T[k];
+                    last_alpha[k] = alpha;
+                    dL_dalpha += (-Tf[k] / (1.0f - alpha)) * bgdot[k];   // background term (backward.cu:531-534)
+                    const float dL_dG = B.y * dL_dalpha;                // straight through the 0.99 cap (:499, :541)
+                    const float gdx = G * dx, gdy = G * dy;
+                    acc[0] += dL_dG * (-gdx * A.z - gdy * A.w) * ddelx_dx;
+                    acc[1] += dL_dG * (-gdy * B.x - gdx * A.w) * ddely_dy;
+                    acc[2] += -0.5f * gdx * dx * dL_dG;
+                    acc[3] += -0.5f * gdx * dy * dL_dG;
+                    acc[4] += -0.5f * gdy * dy * dL_dG;
+                    acc[5] += G * dL_dalpha;
+                    acc[6] += w * dp0[k];
+                    acc[7] += w * dp1[k];
+                    acc8 += w * dp2[k];
+                }
+            }
+            if (gs2m_ballot_b(any) == 0ull) continue;   // no lane contributed: the row keeps its zeros
+            const float s = bw_reduce8(acc, lane);
+            const float s8 = bw_reduce1(acc8);
+            const unsigned long long row = (unsigned long long)__float_as_uint(Cc.y);
+            if (row < n_rows) {
+                float* dst = rows + (size_t)row * GS2M_BW_ROW;
+                // lane l < 8 holds value 4 (l & 1) + 2 ((l >> 1) & 1) + ((l >> 2) & 1); lane 8 stores the ninth
+                if (lane < 8) dst[4 * (lane & 1) + 2 * ((lane >> 1) & 1) + ((lane >> 2) & 1)] = s;
+                else if (lane == 8) dst[8] = s8;
+            }
+        }
+    }
+}

@@ -1,5 +1,6 @@
 // raster_blend.hip -- compositing stage (default FMA contraction; VALU-bound inner loop).
 #include "raster_blend.h"
+#include "raster_backward_blend.h"
 #include "raster_internal.h"
 
 // gy = rows of the 16 x 16 reference grid; tile_rows = 16 x 16 tiles per instance list (GS2M_OPT_TILE_ROWS)
@@ -44,4 +45,13 @@ int gs2m_launch_blend(hipStream_t st, int variant, int tile_rows, int nv, int gx
     }
     gs2m_set_error("blend variant %d is not available with GS2M_OPT_TILE_ROWS %d (variants: 0 [rows 1 only], 4)", variant, tile_rows);
     return 1;
+}
+
+// backward of the compositing (one view, 16 x 16 lists): one wave per tile, four tiles per workgroup
+void gs2m_launch_blend_backward(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
+                                GeomRecs recs, const CamUniform* cams, int P, unsigned cap, const float* dL_dpix,
+                                const unsigned* row_offset, float* rows, unsigned long long n_rows) {
+    const int tiles = gx * gy;
+    GS2M_LAUNCH((k_blend_backward<4>), dim3((tiles + 3) / 4), dim3(256), 0, st, keys, tile_start, recs, cams, P, cap, dL_dpix,
+                row_offset, rows, n_rows);
 }

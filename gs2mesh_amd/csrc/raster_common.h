@@ -15,6 +15,9 @@
 #define GS2M_SCHED_CH 2
 #endif
 #define GS2M_SCHED_CHUNK (GS2M_SCHED_CW * GS2M_SCHED_CH)
+// floats per instance row of the backward pass (48 B = three 16-B vectors): mx my | ca cb cc | op | r g b | 3 pad
+// (raster_backward_blend.h writes the rows, raster_backward_project.h sums them)
+#define GS2M_BW_ROW 12
 
 // Per-view uniforms (the per-view fields of GaussianRasterizationSettings,
 // DGR/diff_gaussian_rasterization/__init__.py:157-169, + derived focal / tile grid,

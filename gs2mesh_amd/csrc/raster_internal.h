@@ -40,5 +40,27 @@ int gs2m_launch_blend(hipStream_t st, int variant, int tile_rows, int nv, int gx
                       unsigned cap, float* out_color, unsigned char* out_rgb8, const int* rank, const unsigned* order,
                       int mode, unsigned long long* prof, int interleave_views);
 
+// ---- backward pass (gs2m_rasterize_backward): outputs of the per-Gaussian kernel, device pointers
+struct BwOut {
+    float* dL_dmean2D;   // [P,3]
+    float* dL_dconic;    // null or [P,4]: {a, b, 0, c} (the reference's [P,2,2] tap)
+    float* dL_dopacity;  // [P]
+    float* dL_dcolor;    // [P,3]
+    float* dL_dmean3D;   // [P,3]
+    float* dL_dcov3D;    // [P,6]
+    float* dL_dsh;       // null or [P,M,3]
+    float* dL_dscale;    // [P,3]
+    float* dL_drot;      // [P,4]
+};
+// exclusive scan of the records' tile-rect areas -> row_offset[P] (first instance row of every Gaussian), *total_rows = their sum;
+// block_sum = scratch of ceil(P / 256) words
+void gs2m_launch_bw_row_offsets(hipStream_t st, GeomRecs recs, int P, unsigned* block_sum, unsigned* row_offset,
+                                unsigned long long* total_rows);
+void gs2m_launch_blend_backward(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
+                                GeomRecs recs, const CamUniform* cams, int P, unsigned cap, const float* dL_dpix,
+                                const unsigned* row_offset, float* rows, unsigned long long n_rows);
+void gs2m_launch_gaussian_backward(hipStream_t st, const GaussIn& g, const CamUniform* cams, GeomRecs recs,
+                                   const unsigned* row_offset, const float* rows, unsigned long long n_rows, const BwOut& out);
+
 // error plumbing (common_api.hip)
 void gs2m_set_error(const char* fmt, ...);

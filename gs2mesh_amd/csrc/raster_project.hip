@@ -1,5 +1,6 @@
 // raster_project.hip -- projection / counting / scatter stage (compiled with -ffp-contract=off).
 #include "raster_project.h"
+#include "raster_backward_project.h"
 #include "raster_internal.h"
 
 // k_count_tiles: threads per workgroup = the workgroup's chunk of Gaussians, at most 1024
@@ -124,4 +125,17 @@ void gs2m_launch_pack_camera(hipStream_t st, CamUniform* cams, int slot, const f
                              float tanfovy, int W, int H, int th) {
     GS2M_LAUNCH(k_pack_camera, dim3(1), dim3(64), 0, st, cams, slot, viewmatrix, projmatrix, campos, bg, tanfovx,
                 tanfovy, W, H, th);
+}
+
+void gs2m_launch_bw_row_offsets(hipStream_t st, GeomRecs recs, int P, unsigned* block_sum, unsigned* row_offset,
+                                unsigned long long* total_rows) {
+    const int nb = (P + 255) / 256;
+    GS2M_LAUNCH(k_bw_area_block_sums, dim3(nb), dim3(256), 0, st, recs, P, block_sum);
+    GS2M_LAUNCH(k_bw_scan_blocks, dim3(1), dim3(256), 0, st, block_sum, nb, total_rows);
+    GS2M_LAUNCH(k_bw_row_offsets, dim3(nb), dim3(256), 0, st, recs, P, (const unsigned*)block_sum, row_offset);
+}
+
+void gs2m_launch_gaussian_backward(hipStream_t st, const GaussIn& g, const CamUniform* cams, GeomRecs recs,
+                                   const unsigned* row_offset, const float* rows, unsigned long long n_rows, const BwOut& out) {
+    GS2M_LAUNCH(k_gaussian_backward, dim3((g.P + 255) / 256), dim3(256), 0, st, g, cams, recs, row_offset, rows, n_rows, out);
 }

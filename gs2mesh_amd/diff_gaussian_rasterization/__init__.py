@@ -1,5 +1,5 @@
 """Operator-level drop-in for the reference's ``diff_gaussian_rasterization`` module
-(DGR/diff_gaussian_rasterization/__init__.py), forward pass only.
+(DGR/diff_gaussian_rasterization/__init__.py): forward pass and, for 3DGS training, the backward pass.
 
 Same public names, argument meaning and error behaviour:
 
@@ -11,7 +11,12 @@ Same public names, argument meaning and error behaviour:
 ``GS/gaussian_renderer/__init__.py:14`` imports exactly these two names, so putting this package on
 ``sys.path`` as ``diff_gaussian_rasterization`` makes the reference's ``render()`` run
 on the HIP kernels unchanged.  The hot path runs under ``torch.no_grad()``
-(gs2mesh_utils/renderer_utils.py:374); the backward pass (3DGS training) is out of scope and raises.
+(gs2mesh_utils/renderer_utils.py:374) and takes the plain forward.  When gradients are enabled and an input requires grad, the
+call goes through ``_RasterizeGaussians`` (the reference's autograd Function, DGR __init__.py:44-155: same signature, same
+gradient tuple): ``loss.backward()`` fills ``.grad`` of means3D, means2D (NDC-scaled, what densification reads), shs /
+colors_precomp, opacities, scales, rotations and cov3D_precomp with the reference's gradients (``gs2m_rasterize_backward``).
+The forward state the backward needs stays in the per-device handle; if another forward ran on the handle in between, the
+backward first replays its own forward into a scratch image, so correctness never depends on call order.
 All tensors must be float32, contiguous and on the HIP device; outputs are freshly allocated.
 """
 from __future__ import annotations
@@ -56,19 +61,27 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
+def _none_if_empty(t):
+    return None if t is None or t.numel() == 0 else _f32c(t)
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings):
-    """DGR __init__.py:21-44 / _RasterizeGaussians.forward :46-98 (forward only)."""
-    if any(t is not None and isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled()
-           for t in (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)):
-        raise NotImplementedError(
-            "gs2mesh_amd implements the forward rasteriser only (the GS2Mesh hot path runs under "
-            "torch.no_grad(), renderer_utils.py:374); 3DGS training gradients are out of scope")
+    """DGR __init__.py:21-44.  Gradients wanted: the autograd Function; otherwise the plain forward."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (
+            means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)):
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         raster_settings)
+    return _rasterize_no_grad(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+
+
+def _rasterize_no_grad(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+    """_RasterizeGaussians.forward (DGR __init__.py:46-98) without a graph."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")   # rasterize_points.cu:57-59
     rs = raster_settings
     h = _handle(means3D.device)
-    none_if_empty = lambda t: None if t is None or t.numel() == 0 else _f32c(t)
+    none_if_empty = _none_if_empty
     if rs.debug:
         # the reference's debug mode (DGR __init__.py:83-90): keep a host copy of every argument and, if the rasteriser
         # fails, leave it in snapshot_fw.dump for post-mortem; the C ABI call itself runs with a sync + check per launch
@@ -94,6 +107,61 @@ def _forward(h, rs, means3D, sh, colors_precomp, opacities, scales, rotations, c
         sh_degree=int(rs.sh_degree), scale_modifier=float(rs.scale_modifier), prefiltered=bool(rs.prefiltered),
         debug=bool(rs.debug))
     return color, radii
+
+
+class _RasterizeGaussians(torch.autograd.Function):
+    """DGR __init__.py:44-155.  The reference keeps its three byte arenas in ``ctx``; here the forward state lives in the
+    per-device handle, and ``ctx`` keeps the inputs and the handle's call count."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        color, radii = _rasterize_no_grad(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                          raster_settings)
+        h = _handle(means3D.device)
+        ctx.raster_settings = raster_settings
+        ctx.handle = h
+        ctx.state_calls = h.state_calls
+        ctx.opacity_shape = tuple(opacities.shape)
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities)
+        ctx.mark_non_differentiable(radii)
+        return color, radii
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _):
+        rs = ctx.raster_settings
+        h = ctx.handle
+        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities = ctx.saved_tensors
+        args = dict(shs=_none_if_empty(sh), colors_precomp=_none_if_empty(colors_precomp), scales=_none_if_empty(scales),
+                    rotations=_none_if_empty(rotations), cov3D_precomp=_none_if_empty(cov3Ds_precomp), sh_degree=int(rs.sh_degree),
+                    scale_modifier=float(rs.scale_modifier), debug=bool(rs.debug))
+        cam = (_f32c(rs.viewmatrix), _f32c(rs.projmatrix), _f32c(rs.campos), _f32c(rs.bg), int(rs.image_width),
+               int(rs.image_height), float(rs.tanfovx), float(rs.tanfovy))
+
+        def run():
+            if h.state_calls != ctx.state_calls:
+                # another forward (or render_views) has overwritten the handle's state since ours: replay ours into a scratch
+                # image (two forwards before one backward, several views per optimiser step, another user of the handle)
+                h.forward(_f32c(means3D), _f32c(opacities).reshape(-1), *cam, prefiltered=bool(rs.prefiltered), **args)
+                ctx.state_calls = h.state_calls
+            return h.backward(_f32c(grad_out_color), _f32c(means3D), *cam, **args)
+
+        if rs.debug:
+            keep = tuple(t.detach().cpu().clone() if isinstance(t, torch.Tensor) else t for t in (
+                rs.bg, means3D, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+                rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, rs.debug))
+            try:
+                g = run()
+            except Exception as ex:
+                torch.save(keep, "snapshot_bw.dump")
+                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+                raise ex
+        else:
+            g = run()
+        given = lambda t: t is not None and t.numel() > 0
+        # DGR __init__.py:143-153: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings
+        return (g["mean3D"], g["mean2D"], g["sh"] if given(sh) else None, g["color"] if given(colors_precomp) else None,
+                g["opacity"].reshape(ctx.opacity_shape), g["scale"] if given(scales) else None,
+                g["rot"] if given(rotations) else None, g["cov3D"] if given(cov3Ds_precomp) else None, None)
 
 
 class GaussianRasterizer(nn.Module):

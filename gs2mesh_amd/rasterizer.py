@@ -146,6 +146,9 @@ class Rasterizer:
         self._h = h
         self.device = device
         self.last_num_rendered = None
+        # calls that overwrote or freed the handle's forward state (``forward``, ``render_views``, ``reserve``): a caller that wants to run
+        # ``backward`` later keeps the value it saw after its own forward and compares (diff_gaussian_rasterization)
+        self.state_calls = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -162,6 +165,7 @@ class Rasterizer:
         _lib.check(self._lib.gs2m_raster_set_option(self._h, option, value), self._lib)
 
     def reserve(self, P, n_views, W, H, instances):
+        self.state_calls += 1   # growing an arena frees the forward state: a later ``backward`` must see it gone
         _lib.check(self._lib.gs2m_raster_reserve(self._h, int(P), int(n_views), int(W), int(H), int(instances)),
                    self._lib)
 
@@ -200,6 +204,7 @@ class Rasterizer:
         D = int(sh_degree)
         M = 0 if shs is None or (hasattr(shs, "numel") and shs.numel() == 0) or getattr(shs, "size", 1) == 0 \
             else int(shs.shape[1])
+        self.state_calls += 1
         out = _empty(means3D, (3, int(H), int(W)), np.float32)
         radii = _empty(means3D, (P,), np.int32)
         st = _stream_of(means3D, stream)
@@ -226,6 +231,43 @@ class Rasterizer:
                     raise RuntimeError("instance arena overflow persists after growing")
             self.last_num_rendered = nr[0]
         return out, radii
+
+    def backward(self, dL_dpix, means3D, viewmatrix, projmatrix, campos, bg, W, H, tanfovx, tanfovy, shs=None,
+                 colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, sh_degree=3, scale_modifier=1.0,
+                 debug=False, want_conic=False, stream=None):
+        """``gs2m_rasterize_backward``: gradients of the LAST ``forward`` on this handle, which must have been called with
+        the same inputs (``state_calls`` tells whether another ``forward`` / ``render_views`` ran since).  ``dL_dpix``
+        [3,H,W].  Returns a dict of freshly allocated arrays: mean2D[P,3] (NDC-scaled, z = 0), opacity[P], color[P,3],
+        mean3D[P,3], cov3D[P,6], sh[P,M,3] (None with ``colors_precomp``), scale[P,3], rot[P,4], and conic[P,4] with
+        ``want_conic``.  Every array is written in full; synchronises the stream once."""
+        P = int(means3D.shape[0])
+        D = int(sh_degree)
+        M = 0 if shs is None or (hasattr(shs, "numel") and shs.numel() == 0) or getattr(shs, "size", 1) == 0 \
+            else int(shs.shape[1])
+        st = _stream_of(means3D, stream)
+        f32 = torch.float32 if _is_torch(means3D) else None
+        g = dict(mean2D=_empty(means3D, (P, 3), np.float32), opacity=_empty(means3D, (P,), np.float32),
+                 color=_empty(means3D, (P, 3), np.float32), mean3D=_empty(means3D, (P, 3), np.float32),
+                 cov3D=_empty(means3D, (P, 6), np.float32), scale=_empty(means3D, (P, 3), np.float32),
+                 rot=_empty(means3D, (P, 4), np.float32),
+                 sh=_empty(means3D, (P, M, 3), np.float32) if M else None,
+                 conic=_empty(means3D, (P, 4), np.float32) if want_conic else None)
+        _lib.check(self._lib.gs2m_rasterize_backward(
+            self._h, P, D, M, int(self.last_num_rendered or 0), _ptr(bg, f32, "bg"), int(W), int(H),
+            _ptr(means3D, f32, "means3D"), _ptr(shs, f32, "shs"), _ptr(colors_precomp, f32, "colors_precomp"),
+            _ptr(scales, f32, "scales"), float(scale_modifier), _ptr(rotations, f32, "rotations"),
+            _ptr(cov3D_precomp, f32, "cov3D_precomp"), _ptr(viewmatrix, f32, "viewmatrix"),
+            _ptr(projmatrix, f32, "projmatrix"), _ptr(campos, f32, "campos"), float(tanfovx), float(tanfovy),
+            _ptr(dL_dpix, f32, "dL_dpix"), _ptr(g["mean2D"]), _ptr(g["conic"]), _ptr(g["opacity"]), _ptr(g["color"]),
+            _ptr(g["mean3D"]), _ptr(g["cov3D"]), _ptr(g["sh"]), _ptr(g["scale"]), _ptr(g["rot"]), int(bool(debug)), st),
+            self._lib)
+        return g
+
+    def backward_rows(self):
+        """-> (instance rows of the last ``backward``, bytes of the handle's row arena; 0 = never allocated)."""
+        rows, nbytes = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.gs2m_raster_backward_rows(self._h, C.byref(rows), C.byref(nbytes)), self._lib)
+        return int(rows.value), int(nbytes.value)
 
     def mark_visible(self, positions, viewmatrix, projmatrix, stream=None):
         P = int(positions.shape[0])
@@ -293,6 +335,7 @@ class Rasterizer:
         P = int(xyz.shape[0])
         n = len(cams)
         W, H = cams[0].width, cams[0].height
+        self.state_calls += 1
         g = self._gaussians_struct(gaussians)
         cam_arr = (_lib.Camera * n)(*cams)
         bg_arr = (C.c_float * 3)(*[float(b) for b in bg])

@@ -167,6 +167,53 @@ int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const float* bac
                            float tan_fovy, int prefiltered, float* out_color, int* radii,
                            int debug, gs2m_stream stream);
 
+/*
+ * Backward pass of the LAST gs2m_rasterize_forward on this handle (3DGS training gradients).  Replaces
+ * CudaRasterizer::Rasterizer::backward (rasterizer.h:55-84, rasterizer_impl.cu:338-434): same argument meaning and order,
+ * minus `radii` and the three arenas (the projected records, the sorted per-tile lists and the ranges are still in the
+ * handle) plus the handle and the stream.  The inputs must be the ones the forward was called with.
+ *
+ *   R                 num_rendered of the forward (informational: the handle knows it)
+ *   dL_dpix[3,H,W]    device, gradient of the loss by the forward's out_color
+ *   dL_dmean2D[P,3]   device: NDC-scaled (0.5 W, 0.5 H), z = 0 -- what training's densification reads from means2D.grad
+ *   dL_dconic[P,4]    device or NULL: {a, b, 0, c} (the reference's [P,2,2] intermediate; a tap).  As in the reference, b is
+ *                     HALF the derivative by conic.y (backward.cu:550; its cov2D formulas expect that)
+ *   dL_dopacity[P], dL_dcolor[P,3], dL_dmean3D[P,3], dL_dcov3D[P,6], dL_dscale[P,3], dL_drot[P,4]   device
+ *   dL_dsh[P,M,3]     device (required with shs; coefficients beyond (D+1)^2 get zeros)
+ * Every output is written completely; Gaussians the forward culled get zeros.  dL_dscale / dL_drot are zero with
+ * cov3D_precomp, dL_dsh is untouched with colors_precomp.
+ *
+ * The gradients are the reference's, including where its backward departs from the true derivative (straight-through
+ * 0.99 alpha cap, 1e-7 in the conic inverse, no gradient through clamped tx / ty and clamped SH channels, the background
+ * term; backward.cu:499, :203, :175-176, :32-34, :531-534), with one exception: dL_dscale carries the factor
+ * scale_modifier, which the reference omits (backward.cu:321-325) -- identical at scale_modifier = 1.
+ * The per-pixel contributions are summed WITHOUT float atomics (one row per (Gaussian, tile) instance, then a per-Gaussian
+ * sum in a fixed order): two calls on the same state give bit-identical results.  The row buffer lives in the handle's
+ * grow-only arenas (48 B per instance; gs2m_raster_backward_rows).
+ *
+ * Errors: no gs2m_rasterize_forward state in the handle (e.g. after gs2m_render_views), P / width / height different
+ * from that call, GS2M_OPT_TILE_ROWS 2, GS2M_OPT_PAIR_BATCH > 1, an overflowed forward.  GS2M_OPT_EXACT_TILE_CULL 0 / 1 / 2
+ * all work (a culled instance has alpha < 1/255 on its whole tile: zero gradient).  Synchronises the stream once (the
+ * row count sizes the arena).
+ *
+ * STATED TOLERANCE: against an fp64 statement of the reference's forward differentiated by autograd
+ * (tests/raster_statement.py; loss = sum(w * image), pixels with a threshold decision within 1e-4 excluded), every
+ * gradient tensor is within 4 x the error of the SAME statement evaluated in fp32, in max|g - g64| / max|g64| and in
+ * relative L2 (tests/test_raster_backward.py).  Measured on MI355X: e32 1e-6 .. 1.1e-5, the kernels at most 1.08 x e32
+ * (profiles/raster_backward.txt).
+ */
+int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int R, const float* background,
+                            int width, int height, const float* means3D, const float* shs,
+                            const float* colors_precomp, const float* scales, float scale_modifier,
+                            const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                            const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                            const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                            float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                            float* dL_dscale, float* dL_drot, int debug, gs2m_stream stream);
+
+/* Instance rows of the last gs2m_rasterize_backward call and the bytes of the row arena (0: never allocated). */
+int gs2m_raster_backward_rows(gs2m_raster* r, int64_t* rows, int64_t* arena_bytes);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:26-31,
  * rasterizer_impl.cu:54-66,141-153).  present[P]: device, 1 byte per Gaussian. */
 int gs2m_mark_visible(int P, const float* means3D, const float* viewmatrix,
