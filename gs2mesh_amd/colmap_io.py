@@ -45,6 +45,20 @@ def read_image_poses_text(path):
     return ids, poses, [recs[k][2] for k in ids]
 
 
+def read_points3D_text(path):
+    """sparse/0/points3D.txt (POINT3D_ID X Y Z R G B ERROR TRACK[]...) -> (xyz [N,3] f64, rgb [N,3] u8, error [N])
+    (GS/scene/colmap_loader.py:83-123)."""
+    rows = []
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if not line or line.startswith("#"):
+                continue
+            rows.append(line.split()[1:8])
+    a = np.array(rows, np.float64).reshape(-1, 7)
+    return a[:, 0:3], a[:, 3:6].astype(np.uint8), a[:, 6]
+
+
 def poses_from_file(extrinsic_file):
     """colmap_utils.py:26-42: [N,3,4] world->camera, sorted by image id."""
     return read_image_poses_text(extrinsic_file)[1]

@@ -17,6 +17,7 @@
 #include "platform.h"
 #include "mask_kernels.h"
 #include "sgm_kernels.h"
+#include "knn_kernels.h"
 
 void gs2m_set_error(const char* fmt, ...);
 
@@ -133,5 +134,32 @@ extern "C" int gs2m_stereo_sgm(const uint8_t* left_rgb8, const uint8_t* right_rg
     if (!disp_lr && !disp_rl && !tap_cost_lr) return 0;
     sgm_launch((hipStream_t)stream, left_rgb8, right_rgb8, width, height, max_disparity, p1, p2, disp_lr, disp_rl,
                sgm_scratch_layout(scratch, width, height, max_disparity), tap_cost_lr);
+    return 0;
+}
+
+extern "C" int64_t gs2m_knn_scratch_bytes(int P) { return P <= 0 ? 0 : knn_scratch_layout(nullptr, P).bytes; }
+
+extern "C" int gs2m_knn_mean_dist2(int P, const float* points, const int32_t* order, void* scratch, int64_t scratch_bytes,
+                                   float* out, gs2m_stream stream) {
+    if (P < 0) {
+        gs2m_set_error("gs2m_knn_mean_dist2: P = %d", P);
+        return 1;
+    }
+    if (P == 0) return 0;
+    if (!points || !out) {
+        gs2m_set_error("gs2m_knn_mean_dist2: NULL points or out with P = %d", P);
+        return 1;
+    }
+    const int64_t need = gs2m_knn_scratch_bytes(P);
+    if (!scratch || scratch_bytes < need) {
+        gs2m_set_error("gs2m_knn_mean_dist2: scratch of %lld bytes, gs2m_knn_scratch_bytes asks for %lld",
+                       (long long)(scratch ? scratch_bytes : 0), (long long)need);
+        return 1;
+    }
+    if ((uintptr_t)scratch & 15u) {
+        gs2m_set_error("gs2m_knn_mean_dist2: scratch must be 16-byte aligned");
+        return 1;
+    }
+    knn_launch((hipStream_t)stream, P, points, order, knn_scratch_layout(scratch, P), out);
     return 0;
 }

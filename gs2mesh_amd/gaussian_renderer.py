@@ -1,6 +1,9 @@
 """``render()`` with the reference's signature and return dict (GS/gaussian_renderer/__init__.py:18-100),
-forward only, on the HIP rasteriser.  Kept for callers that hold a 3DGS ``Camera``-like object and a
-``GaussianModel``; the pipeline class ``Renderer`` uses the fused stereo entry point instead."""
+on the HIP rasteriser.  For callers that hold a 3DGS ``Camera``-like object and a ``GaussianModel``: the training loop
+(``gs2mesh_amd.training``) and anything written against the reference's ``render``; the pipeline class ``Renderer`` uses the
+fused stereo entry point instead.  Under ``torch.no_grad()``, or with a model whose tensors do not require grad (``load_ply`` /
+``load_arrays``), it is the plain forward; otherwise the rasteriser records the graph and ``viewspace_points`` carries the
+screen-space gradient densification reads."""
 from __future__ import annotations
 
 import math
@@ -17,7 +20,6 @@ def _dev(x, device):
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None):
     """Background tensor (bg_color) must be on the GPU, as in the reference."""
     device = pc.get_xyz.device
-    screenspace_points = torch.zeros_like(pc.get_xyz)       # gradient carrier in the reference (:26); unused
     tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
     tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
     raster_settings = GaussianRasterizationSettings(
@@ -49,9 +51,19 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
             shs = pc.get_features
     else:
         colors_precomp = override_color
-    with torch.no_grad():
-        rendered_image, radii = rasterizer(means3D=pc.get_xyz, means2D=screenspace_points, shs=shs,
-                                           colors_precomp=colors_precomp, opacities=pc.get_opacity, scales=scales,
+    means3D, opacity = pc.get_xyz, pc.get_opacity
+    want_grad = torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in (means3D, opacity, shs, colors_precomp, scales, rotations, cov3D_precomp))
+    if want_grad:
+        # the reference's gradient carrier (:26-30): the rasteriser's backward leaves d loss / d (screen position) in its .grad,
+        # which GaussianModel.add_densification_stats reads
+        screenspace_points = torch.zeros_like(means3D, requires_grad=True)
+        screenspace_points.retain_grad()
+    else:
+        screenspace_points = torch.zeros_like(means3D)
+    with torch.enable_grad() if want_grad else torch.no_grad():
+        rendered_image, radii = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs,
+                                           colors_precomp=colors_precomp, opacities=opacity, scales=scales,
                                            rotations=rotations, cov3D_precomp=cov3D_precomp)
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
             "radii": radii}

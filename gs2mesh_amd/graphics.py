@@ -14,8 +14,16 @@ is handed to the kernels as a ``gs2m_camera`` host struct.
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import numpy as np
+
+
+class BasicPointCloud(NamedTuple):
+    """GS/utils/graphics_utils.py:17-20: what ``GaussianModel.create_from_pcd`` takes ([P,3] arrays; colours in [0,1])"""
+    points: np.ndarray
+    colors: np.ndarray
+    normals: np.ndarray
 
 
 def getWorld2View2(R, t, translate=np.array([0.0, 0.0, 0.0]), scale=1.0):

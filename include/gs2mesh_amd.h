@@ -35,7 +35,8 @@ extern "C" {
                             (gs2m_tsdf_block_map / _map_keys / _map_bytes / _replace / _extract_mesh / _mesh_copy,
                             gs2m_mesh_cluster, gs2m_raster_blend_cycles, GS2M_OPT_BLEND_MODE / _PROFILE) + round 6
                             (gs2m_tsdf_flags_device, GS2M_OPT_BIN_LANE_TILES, GS2M_OPT_PROJECT_SHARED_READ, GS2M_OPT_EXACT_TILE_CULL level 2; GS2M_OPT_BLEND_MODE 1
-                            removed).  Added since without a new number: gs2m_stereo_sgm / gs2m_stereo_sgm_scratch_bytes.  The Python binding checks it at
+                            removed).  Added since without a new number: gs2m_stereo_sgm / gs2m_stereo_sgm_scratch_bytes,
+                            gs2m_knn_mean_dist2 / gs2m_knn_scratch_bytes.  The Python binding checks it at
                             load time */
 
 typedef void* gs2m_stream; /* hipStream_t */
@@ -601,6 +602,31 @@ int gs2m_mask_preprocess(int n, int width, int height, const uint8_t* const* obj
 int64_t gs2m_stereo_sgm_scratch_bytes(int width, int height, int max_disparity);
 int gs2m_stereo_sgm(const uint8_t* left_rgb8, const uint8_t* right_rgb8, int width, int height, int max_disparity, int p1, int p2,
                     float* disp_lr, float* disp_rl, void* scratch, int64_t scratch_bytes, uint16_t* tap_cost_lr, gs2m_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* nearest neighbours (simple-knn's distCUDA2, the initial scales of 3DGS training)     */
+/* ------------------------------------------------------------------------------------ */
+
+/*
+ * For every point i of points[P][3] the mean of the three smallest squared distances to the OTHER points
+ * (submodules/simple-knn/simple_knn.cu:131-183).  The exact 3-NN, defined bit for bit:
+ *   - d(i, j) = (dx * dx + dy * dy) + dz * dz in f32, every operation rounded on its own (no FMA);
+ *   - "other" is by index: a duplicate of point i at distance 0 counts;
+ *   - b0 <= b1 <= b2 the three smallest d(i, j), j != i, FLT_MAX where fewer than three exist;
+ *   - out[i] = ((b0 + b1) + b2) / 3.0f  (so P = 3 gives about 1.13e38 and P <= 2 gives +inf, as the reference's arithmetic).
+ *   points                  [P][3] f32 device
+ *   order                   NULL, or [P] int32 device: a permutation of [0, P), position -> index, in which the points are
+ *                           walked.  It affects the speed only (sort along a space-filling curve: whole groups of far points
+ *                           are then culled by their boxes), never the result.  That it is a permutation is the caller's
+ *                           business; an entry outside [0, P) is replaced by its position, so no access leaves the arrays.
+ *   scratch, scratch_bytes  device, 16-byte aligned, at least gs2m_knn_scratch_bytes(P); nothing in it outlives the call
+ *   out                     [P] f32 device, indexed like `points`
+ * P = 0 does nothing and returns 0.  Stateless, asynchronous on `stream`, no allocation; bad arguments return 1 with
+ * gs2m_last_error().
+ */
+int64_t gs2m_knn_scratch_bytes(int P);
+int gs2m_knn_mean_dist2(int P, const float* points, const int32_t* order, void* scratch, int64_t scratch_bytes, float* out,
+                        gs2m_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* PNG encoder (the Renderer's left.png / right.png)               */
