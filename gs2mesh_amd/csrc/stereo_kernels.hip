@@ -5,7 +5,10 @@
 //
 // Per pixel (x, y), following Stereo.get_occlusion_mask's numpy arithmetic (int64 grid - float32
 // disparity promotes to float64; astype(int32) truncates toward zero):
-//   xp   = (int32)((double)x - L[y][x])                      x projected into the right image
+//   xp   = (int32)((double)x - L[y][x])                      x projected into the right image; a pixel whose x - L is NaN
+//                                                             or outside int32 is occluded (what the reference's numpy gives
+//                                                             on x86-64, where that conversion yields INT_MIN; C leaves it
+//                                                             undefined and gfx950 would saturate and turn NaN into 0)
 //   xc   = clip(xp, 0, W-1)
 //   xr   = clip((double)xc + R[y][xc], 0, W-1)                re-projected into the left image
 //   occluded = |x - xr| > threshold  or  xp < 0  or  xp >= W
@@ -31,7 +34,9 @@ k_stereo_depth_occlusion(const float* __restrict__ disp_lr, const float* __restr
     const float l = disp_lr[p];
     if (depth) depth[p] = fb / l;
     if (mask) {
-        const int xp = (int)((double)x - (double)l);
+        const double xd = (double)x - (double)l;
+        const bool in_int32 = xd > -2147483649.0 && xd < 2147483648.0;       // false for NaN
+        const int xp = in_int32 ? (int)xd : -2147483647 - 1;
         const int xc = xp < 0 ? 0 : (xp > W - 1 ? W - 1 : xp);
         double xr = (double)xc + (double)disp_rl[(size_t)y * W + xc];
         xr = xr < 0.0 ? 0.0 : (xr > (double)(W - 1) ? (double)(W - 1) : xr);

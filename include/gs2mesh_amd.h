@@ -546,6 +546,8 @@ int gs2m_mesh_vertex_normals(int device, gs2m_stream stream, int64_t n_vertices,
  *   disp_lr, disp_rl  [H,W] f32 device (disp_rl may be NULL when mask_out is NULL)
  *   depth_out         [H,W] f32 device or NULL
  *   mask_out          [H,W] u8 device or NULL: 1 = visible (the reference returns ~occlusion_mask)
+ * With xp = (int32)(x - disp_lr[y][x]) truncated toward zero: a pixel whose x - disp_lr is NaN or outside int32 is occluded.
+ * (A NaN in disp_rl compares false with every threshold, so it occludes none of the pixels that read it, as in the reference.)
  * The outputs are the `depth` / `mask` inputs of gs2m_tsdf_integrate.  Asynchronous.
  */
 int gs2m_stereo_depth_occlusion(const float* disp_lr, const float* disp_rl, int width, int height,
