@@ -201,7 +201,12 @@ int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const float* bac
  * (tests/raster_statement.py; loss = sum(w * image), pixels with a threshold decision within 1e-4 excluded), every
  * gradient tensor is within 4 x the error of the SAME statement evaluated in fp32, in max|g - g64| / max|g64| and in
  * relative L2 (tests/test_raster_backward.py).  Measured on MI355X: e32 1e-6 .. 1.1e-5, the kernels at most 1.08 x e32
- * (profiles/raster_backward.txt).
+ * (profiles/raster_backward.txt).  The same bound holds PER GAUSSIAN (error of a Gaussian's gradient over its own largest
+ * entry, floored at 1e-3 of the tensor's) on the designed edge cases of tests/test_raster_backward_edges.py: frustum clamp,
+ * more than 65536 Gaussians, every SH degree with M above it, images below a tile, lists ending at the 64-instance batches,
+ * saturation and the 0.99 cap; an entry whose sum is ill-conditioned is judged by the worst of several fp32 evaluations of
+ * the statement instead, that entry alone (profiles/raster_backward_edges.txt).  SH coefficients above (D + 1)^2 are neither read nor given a gradient
+ * other than zero, whatever they hold.
  */
 int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int R, const float* background,
                             int width, int height, const float* means3D, const float* shs,

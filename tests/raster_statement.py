@@ -74,11 +74,26 @@ def leaves(arrays, dtype=torch.float64):
     return out
 
 
-def render(p, cam, W, H, bg, sh_degree=3, scale_modifier=1.0):
+def render(p, cam, W, H, bg, sh_degree=3, scale_modifier=1.0, *, clamp_passes_gradient=False, pixel_order_seed=None,
+           transmittance_from_back=False):
     """p: dict of tensors means3D[P,3], opacities[P], means2D[P,3] (dummy), shs[P,M,3] | colors_precomp[P,3],
     scales[P,3] + rotations[P,4] | cov3D_precomp[P,6].  cam: graphics.Camera.  -> (image[3,H,W], aux dict of numpy arrays:
     radii[P], rect[P,4], capped = number of (Gaussian, pixel) evaluations that contributed with the 0.99 cap binding, and
-    the intermediate tensors t_rgb, t_conic, t_cov3, whose .grad is filled by backward())."""
+    the intermediate tensors t_rgb, t_conic, t_cov3, whose .grad is filled by backward()).
+    What the edge tests assert their purpose on: per pixel n_contrib[H,W] (position in the tile's list after the last
+    contributor, 0 = none), saturated[H,W] and sat_at[H,W] (list position of the instance that would have taken T below 1e-4,
+    -1 = none); per tile tile_len[gy,gx]; per Gaussian clamped_x / clamped_y[P] (t.x / t.y clamped to the 1.3 tan(fov)
+    frustum), rgb_clamped[P,3] and capped_of[P] (evaluations of the Gaussian that contributed with the cap binding);
+    contributing = number of contributing (Gaussian, pixel) evaluations.
+    clamp_passes_gradient=True makes the clamped t.x / t.y differentiable: the WRONG derivative (not the reference's), there
+    only so that a test can assert that its case tells the two apart.
+    pixel_order_seed: the pixels of every tile are visited in a seeded random order instead of row by row.  The function is the
+    same; what changes is the order in which a Gaussian's gradient is summed over its contributing pixels, so several seeds in
+    fp32 show how far rounding alone moves a gradient (the yardstick of an ill-conditioned sum).
+    transmittance_from_back: T in front of a contributor is T_final divided by the (1 - alpha) of every contributor from it to
+    the last, multiplied up from the BACK of the list -- the order of the reference's backward (T = T / (1 - alpha),
+    backward.cu:503) -- instead of the product from the front.  The same function again; in fp32 the FRONT of a long list now
+    carries the rounding of the whole chain, as it does in any backward that rebuilds T that way."""
     xyz = p["means3D"]
     dt = xyz.dtype
     P = xyz.shape[0]
@@ -123,8 +138,14 @@ def render(p, cam, W, H, bg, sh_degree=3, scale_modifier=1.0):
     safe_z = torch.where(torch.from_numpy(visible), tvz, torch.ones_like(tvz))
     limx, limy = 1.3 * tanx, 1.3 * tany
     txtz, tytz = tvx / safe_z, tvy / safe_z
-    tx = torch.where((txtz < -limx) | (txtz > limx), (txtz.clamp(-limx, limx) * safe_z).detach(), tvx)
-    ty = torch.where((tytz < -limy) | (tytz > limy), (tytz.clamp(-limy, limy) * safe_z).detach(), tvy)
+    out_x, out_y = (txtz < -limx) | (txtz > limx), (tytz < -limy) | (tytz > limy)
+    cl_x, cl_y = txtz.clamp(-limx, limx) * safe_z, tytz.clamp(-limy, limy) * safe_z
+    if clamp_passes_gradient:   # the derivative of min / max as if t.x / t.z alone had been clamped: NOT the contract
+        cl_x, cl_y = cl_x.detach() + (tvx - tvx.detach()), cl_y.detach() + (tvy - tvy.detach())
+    else:
+        cl_x, cl_y = cl_x.detach(), cl_y.detach()
+    tx = torch.where(out_x, cl_x, tvx)
+    ty = torch.where(out_y, cl_y, tvy)
     J00, J02 = fx / safe_z, -(fx * tx) / (safe_z * safe_z)
     J11, J12 = fy / safe_z, -(fy * ty) / (safe_z * safe_z)
     T0 = [vm[0] * J00 + vm[2] * J02, vm[4] * J00 + vm[6] * J02, vm[8] * J00 + vm[10] * J02]
@@ -172,12 +193,20 @@ def render(p, cam, W, H, bg, sh_degree=3, scale_modifier=1.0):
     order = np.lexsort((np.arange(P), depth32))
     order = order[visible[order]]
     image = torch.zeros((3, H, W), dtype=dt)
-    capped = 0
+    capped = contributing = 0
+    capped_of = np.zeros(P, np.int64)
+    n_contrib = np.zeros((H, W), np.int64)
+    sat_at = np.full((H, W), -1, np.int64)
+    tile_len = np.zeros((gy, gx), np.int64)
     for tyi in range(gy):
         for txi in range(gx):
             sel = order[(rect[order, 0] <= txi) & (txi < rect[order, 2]) & (rect[order, 1] <= tyi) & (tyi < rect[order, 3])]
             ys, xs = np.meshgrid(np.arange(tyi * 16, min(tyi * 16 + 16, H)), np.arange(txi * 16, min(txi * 16 + 16, W)), indexing="ij")
             ys, xs = ys.reshape(-1), xs.reshape(-1)
+            if pixel_order_seed is not None:
+                perm = np.random.default_rng([pixel_order_seed, tyi, txi]).permutation(ys.size)
+                ys, xs = ys[perm], xs[perm]
+            tile_len[tyi, txi] = sel.size
             if sel.size == 0:
                 image[:, ys, xs] = bgt[:, None].expand(3, ys.size)
                 continue
@@ -202,11 +231,24 @@ def render(p, cam, W, H, bg, sh_degree=3, scale_modifier=1.0):
             m = valid & ~done
             a_m = torch.where(m, alpha, torch.zeros_like(alpha))
             Tm_incl = torch.cumprod(1.0 - a_m, dim=0)
-            Tm_excl = torch.cat([torch.ones_like(Tm_incl[:1]), Tm_incl[:-1]], dim=0)
+            if transmittance_from_back:
+                Tm_excl = Tm_incl[-1][None, :] / torch.flip(torch.cumprod(torch.flip(1.0 - a_m, [0]), dim=0), [0])
+            else:
+                Tm_excl = torch.cat([torch.ones_like(Tm_incl[:1]), Tm_incl[:-1]], dim=0)
             wgt = a_m * Tm_excl                                      # [n, px]
             col = (rgb[idx].t()[:, :, None] * wgt[None, :, :]).sum(dim=1) + Tm_incl[-1][None, :] * bgt[:, None]
             image[:, ys, xs] = col
-            capped += int((m & (alpha_raw.detach() > 0.99)).sum())
+            cap_here = m & (alpha_raw.detach() > 0.99)
+            capped += int(cap_here.sum())
+            capped_of[sel] += cap_here.sum(dim=1).numpy()
+            contributing += int(m.sum())
+            pos = torch.arange(1, sel.size + 1)[:, None]
+            n_contrib[ys, xs] = (pos * m).max(dim=0).values.numpy()
+            first_sat = torch.where(sat, pos - 1, torch.full_like(pos, sel.size)).min(dim=0).values.numpy()
+            sat_at[ys, xs] = np.where(first_sat < sel.size, first_sat, -1)
             del T_excl
+    rgb_clamped = np.zeros((P, 3), bool) if p.get("colors_precomp") is not None else (rgb.detach() <= 0).numpy()
     return image, dict(radii=radii, rect=rect.astype(np.uint32), capped=capped, visible=visible, t_rgb=rgb, t_conic=(ca, cb, cc),
-                       t_cov3=c3)
+                       t_cov3=c3, n_contrib=n_contrib, saturated=sat_at >= 0, sat_at=sat_at, tile_len=tile_len,
+                       clamped_x=out_x.numpy() & visible, clamped_y=out_y.numpy() & visible, rgb_clamped=rgb_clamped,
+                       contributing=contributing, capped_of=capped_of)
