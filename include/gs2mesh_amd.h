@@ -379,7 +379,12 @@ int gs2m_tsdf_reset(gs2m_tsdf* t, gs2m_stream stream);
  *           (tsdf_utils.py:68-81 object/occlusion masks)
  *   min_depth: depth < min_depth -> 0 before scaling (tsdf_utils.py:83); pass 0 to skip
  *   extrinsic_w2c: HOST, row-major 4x4 float64 world->camera (what the reference passes:
- *           np.linalg.inv(extrinsic_matrix))
+ *           np.linalg.inv(extrinsic_matrix)); a singular matrix is an error
+ * Depths that are not positive after the conversion -- zero, negative, NaN (also NaN * mask), -inf, and +inf under any
+ * depth_trunc, the default inf included (+inf >= inf) -- touch no block and update no voxel, as in Open3D.  The 64 strided
+ * pixels one wavefront of the touch pass handles must span at most 2^24 blocks (the box around all their +-sdf_trunc
+ * cubes): a wider span is not integrated but refused with overflow flag 4, like a block index outside the key range
+ * (tests/test_tsdf_edges.py).
  * Asynchronous.
  */
 int gs2m_tsdf_integrate(gs2m_tsdf* t, const float* depth, const uint8_t* color,

@@ -346,8 +346,10 @@ def test_batch_integrate_is_bit_identical_to_frame_by_frame(backend, color, use_
     """gs2m_tsdf_integrate_batch (voxel-stationary: all frames of the batch in one sweep over the touched blocks) vs the
     per-frame path in the same frame order and vs the oracle: block sets, counts, tsdf and colour sums bit for bit, with
     min-depth, depth scale / truncation and (optionally) per-frame masks; a second batch continues the same volume.  Sweeps of
-    11 / 9 frames: blocks touched by more than four frames take several rounds of the frame-lane sweep (k_tsdf_sweep_fl: four
-    frames per round, ping-pong LDS buffers), a partial last round included."""
+    11 / 9 frames: k_tsdf_integrate_batch gives one 256-thread workgroup a z-quarter of a touched block, keeps the state of
+    its voxels in registers and walks the frames whose bit is set in the block's frame mask in ascending order, probing frame
+    n + 1 (projection + depth gathers) before it applies frame n (a block touched by one, two or three frames leaves that
+    two-deep pipeline by a different exit each)."""
     be = backend
     frs, K = frames(n_frames, 160, 120, 170.0)
     W, H, fx, fy, cx, cy = K
