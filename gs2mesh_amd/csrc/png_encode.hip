@@ -731,20 +731,12 @@ k_png_crc_finish(const PngImg* __restrict__ imgs, const unsigned* __restrict__ t
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-#define PNG_HIPCHK(expr)                                                                                  \
-    do {                                                                                                  \
-        hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) {                                                                          \
-            gs2m_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return 1;                                                                                     \
-        }                                                                                                 \
-    } while (0)
+#include "device_memory.h"
 
 struct gs2m_png {
     int device = 0;
-    unsigned* d_tabs = nullptr;        // [256] CRC-32 byte table, [32] x^(2^k) mod P
-    unsigned char* d_arena = nullptr;  // grow-only scratch
-    size_t arena_cap = 0;
+    DeviceBuffer<unsigned> d_tabs;   // [256] CRC-32 byte table, [32] x^(2^k) mod P
+    ScratchArena arena;              // per-call temporaries, grow-only
 };
 
 static unsigned host_multmodp(unsigned a, unsigned b) {
@@ -761,7 +753,7 @@ extern "C" int gs2m_png_create(gs2m_png** out, int device) {
         gs2m_set_error("gs2m_png_create: out is NULL");
         return 1;
     }
-    PNG_HIPCHK(hipSetDevice(device));
+    GS2M_HIPCHK(hipSetDevice(device));
     unsigned tabs[256 + 32];
     for (unsigned n = 0; n < 256; ++n) {
         unsigned c = n;
@@ -773,10 +765,9 @@ extern "C" int gs2m_png_create(gs2m_png** out, int device) {
     for (int k = 1; k < 32; ++k) tabs[256 + k] = x = host_multmodp(x, x);
     gs2m_png* h = new gs2m_png();
     h->device = device;
-    if (hipMalloc((void**)&h->d_tabs, sizeof(tabs)) != hipSuccess ||
-        hipMemcpy(h->d_tabs, tabs, sizeof(tabs), hipMemcpyHostToDevice) != hipSuccess) {
+    if (h->d_tabs.reserve_exact(256 + 32) ||
+        hipMemcpy(h->d_tabs.get(), tabs, sizeof(tabs), hipMemcpyHostToDevice) != hipSuccess) {
         gs2m_set_error("gs2m_png_create: allocation failed");
-        (void)hipFree(h->d_tabs);
         delete h;
         return 1;
     }
@@ -787,9 +778,7 @@ extern "C" int gs2m_png_create(gs2m_png** out, int device) {
 extern "C" int gs2m_png_destroy(gs2m_png* p) {
     if (!p) return 0;
     (void)hipSetDevice(p->device);
-    (void)hipFree(p->d_tabs);
-    (void)hipFree(p->d_arena);
-    delete p;
+    delete p;   // the table and the arena are members
     return 0;
 }
 
@@ -805,8 +794,6 @@ extern "C" int64_t gs2m_png_max_bytes(int width, int height, int rows_per_segmen
     if (total - 57 > (int64_t)0x7fffffff) return -1;   // the IDAT length is a 31-bit field
     return total;
 }
-
-static size_t png_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 extern "C" int gs2m_png_encode(gs2m_png* p, int n, int width, int height, const uint8_t* rgb8, int64_t image_stride,
                                uint8_t* out, int64_t out_stride, int64_t* out_bytes, int filter, int rows_per_segment,
@@ -837,30 +824,15 @@ extern "C" int gs2m_png_encode(gs2m_png* p, int n, int width, int height, const 
     const int nseg = (height + S - 1) / S;
     const size_t nsegs = (size_t)n * nseg;
     const int max_chunks = (int)((max_bytes + PNG_CRC_CHUNK - 1) / PNG_CRC_CHUNK);
-    const size_t o_codes = png_align(nsegs * sizeof(PngSeg));
-    const size_t o_hdr = o_codes + png_align(nsegs * PNG_CODE_STRIDE * sizeof(unsigned));
-    const size_t o_off = o_hdr + png_align(nsegs * PNG_HDR_WORDS * sizeof(unsigned));
-    const size_t o_img = o_off + png_align(nsegs * sizeof(unsigned long long));
-    const size_t o_crc = o_img + png_align((size_t)n * sizeof(PngImg));
-    const size_t need = o_crc + png_align((size_t)n * max_chunks * sizeof(unsigned));
-    if (need > p->arena_cap) {
-        PNG_HIPCHK(hipSetDevice(p->device));
-        if (p->d_arena) {
-            PNG_HIPCHK(hipFree(p->d_arena));   // synchronises: safe w.r.t. in-flight work
-            p->d_arena = nullptr;
-            p->arena_cap = 0;
-        }
-        const size_t cap = need + need / 8 + 4096;
-        PNG_HIPCHK(hipMalloc((void**)&p->d_arena, cap));
-        p->arena_cap = cap;
-    }
-    PngSeg* segs = reinterpret_cast<PngSeg*>(p->d_arena);
-    unsigned* codes = reinterpret_cast<unsigned*>(p->d_arena + o_codes);
-    unsigned* hdr = reinterpret_cast<unsigned*>(p->d_arena + o_hdr);
-    unsigned long long* seg_off = reinterpret_cast<unsigned long long*>(p->d_arena + o_off);
-    PngImg* imgs = reinterpret_cast<PngImg*>(p->d_arena + o_img);
-    unsigned* chunk_crc = reinterpret_cast<unsigned*>(p->d_arena + o_crc);
-    const unsigned* tabs = p->d_tabs;
+    PngSeg* segs;
+    unsigned *codes, *hdr, *chunk_crc;
+    unsigned long long* seg_off;
+    PngImg* imgs;
+    GS2M_HIPCHK(hipSetDevice(p->device));
+    if (p->arena.carve(arena_sub(segs, nsegs), arena_sub(codes, nsegs * PNG_CODE_STRIDE), arena_sub(hdr, nsegs * PNG_HDR_WORDS),
+                       arena_sub(seg_off, nsegs), arena_sub(imgs, (size_t)n), arena_sub(chunk_crc, (size_t)n * max_chunks)))
+        return 1;
+    const unsigned* tabs = p->d_tabs.get();
     const long long istride = (long long)image_stride, ostride = (long long)out_stride;
     GS2M_LAUNCH(k_png_codes, dim3(nseg, n), dim3(PNG_THREADS), 0, stream, rgb8, istride, width, height, S, filter, nseg,
                 segs, codes, hdr);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/gs2mesh_amd.h"
+#include "device_memory.h"
 #include "raster_internal.h"
 #include "roctx_ranges.h"
 
@@ -25,15 +26,6 @@ void gs2m_set_error(const char* fmt, ...) {
 extern "C" const char* gs2m_last_error(void) { return g_err.c_str(); }
 extern "C" int gs2m_version(void) { return GS2M_VERSION; }
 
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e__ = (expr);                                                              \
-        if (e__ != hipSuccess) {                                                              \
-            gs2m_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 #define GS2M_SORT_CLASSES_API 3   // = GS2M_SORT_CLASSES (raster_sort.h)
 #define GS2M_MAX_STATUS 64  // views per gs2m_render_views call whose status is kept
 
@@ -44,61 +36,39 @@ struct gs2m_raster {
     int opt_blend_profile = 0;
     int opt_project_shared = 0;     // GS2M_OPT_PROJECT_SHARED_READ: 0 auto (by model size), 1 always, 2 never
     int opt_bin_lane_tiles = 4;     // rects of at most this many binning tiles are walked by their own lane (round 6)
-    unsigned long long* d_blend_prof = nullptr;   // [GS2M_BLEND_PROF_COUNTERS] phase-cycle sums of the profile build (GS2M_OPT_BLEND_PROFILE)
-    struct EvPair {
-        int stage;
-        hipEvent_t a, b;
-    };
-    std::vector<EvPair> ev_live;        // recorded, not yet read
-    std::vector<hipEvent_t> ev_free;    // recycled events
-    CamUniform* d_cams = nullptr;  // [GS2M_MAX_PASS_VIEWS]
-    float4* d_recs = nullptr;   // [3 * recs_cap] float4: the 32-B parts of recs_cap records, then their 16-B parts (GeomRecs)
-    size_t recs_cap = 0;  // float4s
-    unsigned long long* d_tilemask = nullptr;
-    float* d_shpack = nullptr;   // wave-transposed SH copy of the Gaussians last passed to gs2m_raster_pack_sh
-    size_t shpack_cap = 0;
+    DeviceBuffer<unsigned long long> d_blend_prof;   // [64][16] phase-cycle sums of the profile build (GS2M_OPT_BLEND_PROFILE), empty until asked for
+    EventPool events;                    // stage timing (GS2M_OPT_STAGE_TIMING)
+    DeviceBuffer<CamUniform> d_cams;     // [GS2M_MAX_PASS_VIEWS]
+    DeviceBuffer<float4> d_recs;         // [3 * n] float4: the 32-B parts of n records, then their 16-B parts (GeomRecs)
+    DeviceBuffer<unsigned long long> d_tilemask;
+    DeviceBuffer<float> d_shpack;        // wave-transposed SH copy of the Gaussians last passed to gs2m_raster_pack_sh
     const float* pack_src = nullptr;
     const float* pack_src_rest = nullptr;
     int pack_P = 0;
     // gs2m_raster_pack_model: spatially ordered packed copy of the per-Gaussian parameters (the SH copy above is then in
     // the same order), order = position -> id, rank = id -> position
-    float* d_pk_xyz = nullptr;
-    float* d_pk_scales = nullptr;
-    float* d_pk_rots = nullptr;
-    float* d_pk_opac = nullptr;
-    int* d_order = nullptr;
-    int* d_rank = nullptr;
-    size_t pk_cap3 = 0, pk_cap3s = 0, pk_cap4 = 0, pk_cap1 = 0, order_cap = 0, rank_cap = 0;
+    DeviceBuffer<float> d_pk_xyz, d_pk_scales, d_pk_rots, d_pk_opac;
+    DeviceBuffer<int> d_order, d_rank;
     const float* model_src[4] = {nullptr, nullptr, nullptr, nullptr};  // xyz, scales, rotations, opacities packed from
     bool model_packed = false;
     bool hint_valid = false;         // h_status holds the class counts of an earlier pass of the same geometry
     bool last_packed = false;        // the last pass ran on the packed copy (parity taps map positions back to ids)
     const int* run_rank = nullptr;   // rank table of the pass being launched (null: keys carry record positions)
-    size_t mask_cap = 0;
-    unsigned* d_hist = nullptr;
-    size_t hist_cap = 0;  // words
-    unsigned* d_tile_count = nullptr;
-    unsigned* d_tile_start = nullptr;
-    size_t tile_cap = 0;  // words per array
-    unsigned* d_sort_lists = nullptr;  // per view, per size class: count + tile ids (k_tile_scan -> k_sort_tiles_*)
-    size_t sort_lists_cap = 0;
-    unsigned long long* d_keys = nullptr;
-    unsigned long long* d_tmp = nullptr;
-    size_t keys_cap_total = 0;  // entries in each of d_keys / d_tmp
+    DeviceBuffer<unsigned> d_hist;
+    DeviceBuffer<unsigned> d_tile_count, d_tile_start;   // [views][tiles + 1]
+    DeviceBuffer<unsigned> d_sort_lists;  // per view, per size class: count + tile ids (k_tile_scan -> k_sort_tiles_*)
+    DeviceBuffer<unsigned long long> d_keys, d_tmp;      // [views][inst_cap]
     unsigned inst_cap = 0;      // per-view capacity requested
     // [1 + GS2M_MAX_STATUS]: slot 0 is STICKY ({max instances any call needed, any call overflowed} since the last
     // gs2m_raster_status), slots 1.. are the views of the last call
-    ViewStatus* d_status = nullptr;  // slot 0: the sticky word (device atomics)
-    ViewStatus* h_status = nullptr;  // pinned, device-mapped: slots 1.. are WRITTEN BY k_tile_scan itself (round 4: no status copy
-                                     // launch behind every pass); slot 0 mirrors the sticky word at gs2m_raster_status
+    DeviceBuffer<ViewStatus> d_status;  // slot 0: the sticky word (device atomics)
+    PinnedBuffer<ViewStatus> h_status;  // device-mapped: slots 1.. are WRITTEN BY k_tile_scan itself (round 4: no status copy
+                                        // launch behind every pass); slot 0 mirrors the sticky word at gs2m_raster_status
     // backward pass (gs2m_rasterize_backward): grow-only arenas, and what the last call left in the forward state
-    float* d_bw_rows = nullptr;          // [rows][GS2M_BW_ROW] one row per (Gaussian, tile of its rect)
-    size_t bw_rows_cap = 0;              // floats
-    unsigned* d_bw_offset = nullptr;     // [P] first row of every Gaussian
-    size_t bw_offset_cap = 0;
-    unsigned* d_bw_blocks = nullptr;     // [ceil(P / 256)] scan scratch
-    size_t bw_blocks_cap = 0;
-    unsigned long long* d_bw_total = nullptr;
+    DeviceBuffer<float> d_bw_rows;          // [rows][GS2M_BW_ROW] one row per (Gaussian, tile of its rect)
+    DeviceBuffer<unsigned> d_bw_offset;     // [P] first row of every Gaussian
+    DeviceBuffer<unsigned> d_bw_blocks;     // [ceil(P / 256)] scan scratch
+    DeviceBuffer<unsigned long long> d_bw_total;   // [1]
     unsigned long long bw_last_rows = 0;  // instance rows of the last backward call
     bool fw_valid = false;               // the state is that of ONE gs2m_rasterize_forward call
     int fw_P = 0, fw_W = 0, fw_H = 0, fw_tile_rows = 1;
@@ -107,72 +77,28 @@ struct gs2m_raster {
     unsigned last_cap = 0;
 };
 
-template <typename T>
-static int ensure(T** p, size_t* cap, size_t need) {
-    if (need <= *cap && *p) return 0;
-    if (*p) {
-        HIPCHK(hipFree(*p));  // synchronises: safe w.r.t. in-flight work
-        *p = nullptr;
-        *cap = 0;
-    }
-    size_t n = need + need / 8 + 64;
-    HIPCHK(hipMalloc((void**)p, n * sizeof(T)));
-    *cap = n;
-    return 0;
-}
-
 extern "C" int gs2m_raster_create(gs2m_raster** out, int device) {
     if (!out) {
         gs2m_set_error("gs2m_raster_create: out is NULL");
         return 1;
     }
-    HIPCHK(hipSetDevice(device));
+    GS2M_HIPCHK(hipSetDevice(device));
     gs2m_raster* r = new gs2m_raster();
     r->device = device;
-    if (hipMalloc((void**)&r->d_cams, sizeof(CamUniform) * GS2M_MAX_PASS_VIEWS) != hipSuccess ||
-        hipMalloc((void**)&r->d_status, sizeof(ViewStatus) * (GS2M_MAX_STATUS + 1)) != hipSuccess ||
-        hipHostMalloc((void**)&r->h_status, sizeof(ViewStatus) * (GS2M_MAX_STATUS + 1)) != hipSuccess ||
-        hipMemset(r->d_status, 0, sizeof(ViewStatus) * (GS2M_MAX_STATUS + 1)) != hipSuccess) {
+    const size_t n_status = GS2M_MAX_STATUS + 1;
+    if (r->d_cams.reserve_exact(GS2M_MAX_PASS_VIEWS) || r->d_status.reserve_exact(n_status) || r->h_status.reserve(n_status) ||
+        hipMemset(r->d_status.get(), 0, sizeof(ViewStatus) * n_status) != hipSuccess) {
         gs2m_set_error("gs2m_raster_create: allocation failed");
-        delete r;
+        delete r;   // frees what had been allocated
         return 1;
     }
-    memset(r->h_status, 0, sizeof(ViewStatus) * (GS2M_MAX_STATUS + 1));
+    memset(r->h_status.get(), 0, sizeof(ViewStatus) * n_status);
     *out = r;
     return 0;
 }
 
 extern "C" int gs2m_raster_destroy(gs2m_raster* r) {
-    if (!r) return 0;
-    (void)hipFree(r->d_cams);
-    (void)hipFree(r->d_recs);
-    (void)hipFree(r->d_tilemask);
-    (void)hipFree(r->d_shpack);
-    (void)hipFree(r->d_pk_xyz);
-    (void)hipFree(r->d_pk_scales);
-    (void)hipFree(r->d_pk_rots);
-    (void)hipFree(r->d_pk_opac);
-    (void)hipFree(r->d_order);
-    (void)hipFree(r->d_rank);
-    (void)hipFree(r->d_hist);
-    (void)hipFree(r->d_tile_count);
-    (void)hipFree(r->d_tile_start);
-    (void)hipFree(r->d_sort_lists);
-    (void)hipFree(r->d_keys);
-    (void)hipFree(r->d_tmp);
-    (void)hipFree(r->d_status);
-    (void)hipFree(r->d_blend_prof);
-    (void)hipFree(r->d_bw_rows);
-    (void)hipFree(r->d_bw_offset);
-    (void)hipFree(r->d_bw_blocks);
-    (void)hipFree(r->d_bw_total);
-    (void)hipHostFree(r->h_status);
-    for (auto& p : r->ev_live) {
-        (void)hipEventDestroy(p.a);
-        (void)hipEventDestroy(p.b);
-    }
-    for (auto e : r->ev_free) (void)hipEventDestroy(e);
-    delete r;
+    delete r;   // every buffer and event is a member
     return 0;
 }
 
@@ -249,10 +175,10 @@ extern "C" int gs2m_raster_set_option(gs2m_raster* r, int option, int value) {
             return 0;
         case GS2M_OPT_BLEND_PROFILE:
             r->opt_blend_profile = value != 0;
-            if (value && !r->d_blend_prof) {
-                HIPCHK(hipSetDevice(r->device));
-                HIPCHK(hipMalloc((void**)&r->d_blend_prof, 64 * 16 * sizeof(unsigned long long)));   // 64 copies, one per 128 B
-                HIPCHK(hipMemset(r->d_blend_prof, 0, 64 * 16 * sizeof(unsigned long long)));
+            if (value && !r->d_blend_prof.get()) {
+                GS2M_HIPCHK(hipSetDevice(r->device));
+                if (r->d_blend_prof.reserve_exact(64 * 16)) return 1;   // 64 copies, one per 128 B
+                GS2M_HIPCHK(hipMemset(r->d_blend_prof.get(), 0, 64 * 16 * sizeof(unsigned long long)));
             }
             return 0;
         default: gs2m_set_error("unknown option %d", option); return 1;
@@ -286,7 +212,7 @@ extern "C" int gs2m_raster_reserve(gs2m_raster* r, int P, int n_views, int W, in
         gs2m_set_error("null handle");
         return 1;
     }
-    HIPCHK(hipSetDevice(r->device));
+    GS2M_HIPCHK(hipSetDevice(r->device));
     // growing an arena frees the projected records / lists / ranges a later gs2m_rasterize_backward would read: whoever calls
     // this ends the forward state (gs2m_rasterize_forward sets it again once its own pass, reserve included, has been launched)
     r->fw_valid = false;
@@ -294,22 +220,20 @@ extern "C" int gs2m_raster_reserve(gs2m_raster* r, int P, int n_views, int W, in
     const int tiles = ((W + GS2M_TILE - 1) / GS2M_TILE) * ((H + GS2M_TILE - 1) / GS2M_TILE);
     int chunk, n_wg;
     geometry(r, P, &chunk, &n_wg);
-    if (ensure(&r->d_recs, &r->recs_cap, 3 * (size_t)nv * (size_t)(P > 0 ? P : 1))) return 1;
-    if (ensure(&r->d_tilemask, &r->mask_cap, (size_t)nv * (size_t)(P > 0 ? P : 1))) return 1;
-    if (ensure(&r->d_hist, &r->hist_cap, (size_t)nv * n_wg * tiles)) return 1;
-    size_t tc = r->tile_cap;
-    if (ensure(&r->d_tile_count, &tc, (size_t)nv * (tiles + 1))) return 1;
-    if (ensure(&r->d_tile_start, &r->tile_cap, (size_t)nv * (tiles + 1))) return 1;
-    if (ensure(&r->d_sort_lists, &r->sort_lists_cap, gs2m_sort_lists_words(nv, tiles))) return 1;
+    if (r->d_recs.reserve(3 * (size_t)nv * (size_t)(P > 0 ? P : 1))) return 1;
+    if (r->d_tilemask.reserve((size_t)nv * (size_t)(P > 0 ? P : 1))) return 1;
+    if (r->d_hist.reserve((size_t)nv * n_wg * tiles)) return 1;
+    if (r->d_tile_count.reserve((size_t)nv * (tiles + 1))) return 1;
+    if (r->d_tile_start.reserve((size_t)nv * (tiles + 1))) return 1;
+    if (r->d_sort_lists.reserve(gs2m_sort_lists_words(nv, tiles))) return 1;
     if (instances > 0xfffffff0ll) {
         gs2m_set_error("instance count %lld exceeds the 32-bit offsets of the binning stage", (long long)instances);
         return 1;
     }
     if (instances > 0 && (unsigned)instances > r->inst_cap) r->inst_cap = (unsigned)instances;
     if (r->inst_cap < 1024) r->inst_cap = 1024;
-    size_t kc = r->keys_cap_total;
-    if (ensure(&r->d_keys, &kc, (size_t)nv * r->inst_cap)) return 1;
-    if (ensure(&r->d_tmp, &r->keys_cap_total, (size_t)nv * r->inst_cap)) return 1;
+    if (r->d_keys.reserve((size_t)nv * r->inst_cap)) return 1;
+    if (r->d_tmp.reserve((size_t)nv * r->inst_cap)) return 1;
     return 0;
 }
 
@@ -324,16 +248,6 @@ static int dbg_check(gs2m_raster* r, hipStream_t st, const char* what) {
     return 0;
 }
 
-static hipEvent_t ev_get(gs2m_raster* r) {
-    if (!r->ev_free.empty()) {
-        hipEvent_t e = r->ev_free.back();
-        r->ev_free.pop_back();
-        return e;
-    }
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
 static const char* const kStageRange[GS2M_N_STAGES] = {"gs2m:project", "gs2m:hist_colscan", "gs2m:tile_scan", "gs2m:scatter",
                                                         "gs2m:sort_tiles", "gs2m:blend", "gs2m:count_tiles"};
 struct StageTimer {  // RAII: a rocTX range (GS2M_ROCTX=1) and, when timing is on, an event pair around one stage launch
@@ -344,15 +258,15 @@ struct StageTimer {  // RAII: a rocTX range (GS2M_ROCTX=1) and, when timing is o
     Gs2mRange range;
     StageTimer(gs2m_raster* r_, hipStream_t st_, int stage_) : r(r_), st(st_), stage(stage_), range(kStageRange[stage_]) {
         if (r->opt_timing) {
-            a = ev_get(r);
-            b = ev_get(r);
+            a = r->events.get();
+            b = r->events.get();
             if (a) (void)hipEventRecord(a, st);
         }
     }
     ~StageTimer() {
         if (a && b) {
             (void)hipEventRecord(b, st);
-            r->ev_live.push_back({stage, a, b});
+            r->events.push(stage, a, b);
         }
     }
 };
@@ -374,18 +288,19 @@ static int run_views(gs2m_raster* r, const GaussIn& g, int nv, int pairs, int W,
     // not written yet reads as the pass before it (or zero: "no information").
     int hint[3] = {-1, -1, -1};
     int interleave = 1;
+    const ViewStatus* hs = r->h_status.get() + 1 + status_slot;
     if (r->hint_valid && r->last_tiles == tiles && r->last_nv == nvt) {
         unsigned nr_max = 0;
         for (int c = 0; c < 3; ++c) {
             unsigned m = 0;
             for (int v = 0; v < nvt; ++v) {
-                const unsigned x = r->h_status[1 + status_slot + v].n_class[c];
+                const unsigned x = hs[v].n_class[c];
                 m = x > m ? x : m;
             }
             hint[c] = m > 0x3fffffffu ? -1 : (int)m;
         }
         for (int v = 0; v < nvt; ++v) {
-            const unsigned x = r->h_status[1 + status_slot + v].num_rendered;
+            const unsigned x = hs[v].num_rendered;
             nr_max = x > nr_max ? x : nr_max;
         }
         // Dispatch order of a multi-view compositing launch: chunk rank major / view minor ("interleaved": the heavy chunks of
@@ -416,52 +331,52 @@ static int run_views(gs2m_raster* r, const GaussIn& g, int nv, int pairs, int W,
     if (gs2m_raster_reserve(r, g.P, nvt, W, H, 0)) return 1;
     const unsigned cap = r->inst_cap;
     // the records of the pass: [nvt * P] 32-B parts, then [nvt * P] 16-B parts
-    const GeomRecs recs{r->d_recs, r->d_recs + 2 * (size_t)nvt * (size_t)g.P};
+    const GeomRecs recs{r->d_recs.get(), r->d_recs.get() + 2 * (size_t)nvt * (size_t)g.P};
     const int cull_arg_p = r->opt_exact_cull, cull_arg_s = r->opt_exact_cull;  // same option for counting and scatter
     // (round 3: projection and counting fused into one kernel -- the counting workgroups projecting their own Gaussians and
     // going on from registers -- measured 51 vs 28 + 28 us on C2 and 212 vs 135 + 80 us on C3: the counting step is bound by
     // its own LDS atomics and tile tests, not by re-reading the records; 128 VGPRs for 1024-thread workgroups.  Not kept.)
     {
         StageTimer tm(r, st, GS2M_STAGE_PROJECT);
-        gs2m_launch_project(nv, pairs, st, g, r->d_cams, recs, out_radii, cull_arg_p, host_cams, r->opt_project_shared);
+        gs2m_launch_project(nv, pairs, st, g, r->d_cams.get(), recs, out_radii, cull_arg_p, host_cams, r->opt_project_shared);
     }
     if (dbg_check(r, st, "project")) return 1;
     {
         StageTimer tm(r, st, GS2M_STAGE_COUNT);
-        if (gs2m_launch_count_tiles(nv, pairs, n_wg, wg_threads, lds_p, st, recs, g.P, r->d_cams, chunk, r->d_hist, r->d_tilemask,
+        if (gs2m_launch_count_tiles(nv, pairs, n_wg, wg_threads, lds_p, st, recs, g.P, r->d_cams.get(), chunk, r->d_hist.get(), r->d_tilemask.get(),
                                     cull_arg_p, g.ids != nullptr, r->opt_bin_lane_tiles))
             return 1;
     }
     if (dbg_check(r, st, "count_tiles")) return 1;
     {
         StageTimer tm(r, st, GS2M_STAGE_COLSCAN);
-        gs2m_launch_hist_colscan(st, nvt, r->d_hist, n_wg, tiles, r->d_tile_count);
+        gs2m_launch_hist_colscan(st, nvt, r->d_hist.get(), n_wg, tiles, r->d_tile_count.get());
     }
     if (dbg_check(r, st, "hist_colscan")) return 1;
     {
         StageTimer tm(r, st, GS2M_STAGE_TILESCAN);
-        gs2m_launch_tile_scan(st, nvt, r->d_tile_count, r->d_tile_start, tiles, gx, r->h_status + 1 + status_slot, r->d_status, cap, r->d_sort_lists);
+        gs2m_launch_tile_scan(st, nvt, r->d_tile_count.get(), r->d_tile_start.get(), tiles, gx, r->h_status.get() + 1 + status_slot, r->d_status.get(), cap, r->d_sort_lists.get());
     }
     if (dbg_check(r, st, "tile_scan")) return 1;
     {
         StageTimer tm(r, st, GS2M_STAGE_SCATTER);
-        if (gs2m_launch_scatter(nv, pairs, n_wg, wg_threads, lds, st, recs, g.P, r->d_cams, chunk, r->d_hist, r->d_tile_start,
-                                r->d_tilemask, r->d_keys, cap, cull_arg_s, g.ids, g.ids != nullptr, r->opt_bin_lane_tiles))
+        if (gs2m_launch_scatter(nv, pairs, n_wg, wg_threads, lds, st, recs, g.P, r->d_cams.get(), chunk, r->d_hist.get(), r->d_tile_start.get(),
+                                r->d_tilemask.get(), r->d_keys.get(), cap, cull_arg_s, g.ids, g.ids != nullptr, r->opt_bin_lane_tiles))
             return 1;
     }
     if (dbg_check(r, st, "scatter")) return 1;
     {
         StageTimer tm(r, st, GS2M_STAGE_SORT);
         // class-grid hint: snapshotted at the top of the pass
-        gs2m_launch_sort_tiles(st, nvt, r->d_keys, r->d_tmp, r->d_tile_start, tiles, cap, r->d_sort_lists, hint);
+        gs2m_launch_sort_tiles(st, nvt, r->d_keys.get(), r->d_tmp.get(), r->d_tile_start.get(), tiles, cap, r->d_sort_lists.get(), hint);
     }
     if (dbg_check(r, st, "sort_tiles")) return 1;
     {
         StageTimer tm(r, st, GS2M_STAGE_BLEND);
-        if (gs2m_launch_blend(st, r->opt_blend, r->opt_tile_rows, nvt, gx, gy, r->d_keys, r->d_tile_start, recs, r->d_cams,
+        if (gs2m_launch_blend(st, r->opt_blend, r->opt_tile_rows, nvt, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, r->d_cams.get(),
                               g.P, cap, out_color, out_rgb8, g.ids ? r->run_rank : nullptr,
-                              r->d_sort_lists + (size_t)nvt * GS2M_SORT_CLASSES_API * (tiles + 1), r->opt_blend_mode,
-                              r->opt_blend_profile ? r->d_blend_prof : nullptr, interleave))
+                              r->d_sort_lists.get() + (size_t)nvt * GS2M_SORT_CLASSES_API * (tiles + 1), r->opt_blend_mode,
+                              r->opt_blend_profile ? r->d_blend_prof.get() : nullptr, interleave))
             return 1;
     }
     if (dbg_check(r, st, "blend")) return 1;
@@ -487,7 +402,7 @@ extern "C" int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const
         return 1;
     }
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(r->device));
+    GS2M_HIPCHK(hipSetDevice(r->device));
     if (width <= 0 || height <= 0 || !out_color) {
         gs2m_set_error("gs2m_rasterize_forward: bad image arguments");
         return 1;
@@ -500,8 +415,8 @@ extern "C" int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const
     r->fw_valid = false;
     if (P == 0) {
         // rasterize_points.cu:68,81: the zero-filled image is returned untouched
-        HIPCHK(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * (size_t)width * height, st));
-        HIPCHK(hipMemsetAsync(r->h_status + 1, 0, sizeof(ViewStatus), st));   // stream-ordered like a pass's own status write
+        GS2M_HIPCHK(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * (size_t)width * height, st));
+        GS2M_HIPCHK(hipMemsetAsync(r->h_status.get() + 1, 0, sizeof(ViewStatus), st));   // stream-ordered like a pass's own status write
         r->last_P = 0;
         r->last_nv = 1;
         r->fw_valid = true;
@@ -546,7 +461,7 @@ extern "C" int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const
     g.scale_modifier = scale_modifier;
     const int saved_debug = r->opt_debug;
     if (debug) r->opt_debug = 1;
-    gs2m_launch_pack_camera(st, r->d_cams, 0, viewmatrix, projmatrix, cam_pos, background, tan_fovx, tan_fovy,
+    gs2m_launch_pack_camera(st, r->d_cams.get(), 0, viewmatrix, projmatrix, cam_pos, background, tan_fovx, tan_fovy,
                             width, height, 16 * r->opt_tile_rows);
     int rc = run_views(r, g, 1, 1, width, height, out_color, nullptr, radii, 0, st, nullptr);
     r->opt_debug = saved_debug;
@@ -576,7 +491,7 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
         return 1;
     }
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(r->device));
+    GS2M_HIPCHK(hipSetDevice(r->device));
     if (!r->fw_valid) {
         gs2m_set_error("gs2m_rasterize_backward: the handle holds no state of a gs2m_rasterize_forward call (the last call was "
                        "gs2m_render_views or gs2m_raster_reserve, or none)");
@@ -626,18 +541,18 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
         ~Restore() { r->opt_debug = v; }
     } restore{r, saved_debug};
     const int gx = (width + GS2M_TILE - 1) / GS2M_TILE, gy = (height + GS2M_TILE - 1) / GS2M_TILE;
-    const GeomRecs recs{r->d_recs, r->d_recs + 2 * (size_t)P};
-    if (ensure(&r->d_bw_offset, &r->bw_offset_cap, (size_t)P)) return 1;
-    if (ensure(&r->d_bw_blocks, &r->bw_blocks_cap, (size_t)(P + 255) / 256)) return 1;
-    if (!r->d_bw_total) HIPCHK(hipMalloc((void**)&r->d_bw_total, sizeof(unsigned long long)));
-    gs2m_launch_pack_camera(st, r->d_cams, 0, viewmatrix, projmatrix, cam_pos, background, tan_fovx, tan_fovy, width, height, 16);
-    gs2m_launch_bw_row_offsets(st, recs, P, r->d_bw_blocks, r->d_bw_offset, r->d_bw_total);
+    const GeomRecs recs{r->d_recs.get(), r->d_recs.get() + 2 * (size_t)P};
+    if (r->d_bw_offset.reserve((size_t)P)) return 1;
+    if (r->d_bw_blocks.reserve((size_t)(P + 255) / 256)) return 1;
+    if (r->d_bw_total.reserve_exact(1)) return 1;
+    gs2m_launch_pack_camera(st, r->d_cams.get(), 0, viewmatrix, projmatrix, cam_pos, background, tan_fovx, tan_fovy, width, height, 16);
+    gs2m_launch_bw_row_offsets(st, recs, P, r->d_bw_blocks.get(), r->d_bw_offset.get(), r->d_bw_total.get());
     if (dbg_check(r, st, "backward row offsets")) return 1;
     // the row count sizes the arena: one host round trip (the reference's forward reads num_rendered the same way)
     unsigned long long n_rows = 0ull;
-    HIPCHK(hipMemcpyAsync(&n_rows, r->d_bw_total, sizeof(n_rows), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (r->h_status[1].overflow) {
+    GS2M_HIPCHK(hipMemcpyAsync(&n_rows, r->d_bw_total.get(), sizeof(n_rows), hipMemcpyDeviceToHost, st));
+    GS2M_HIPCHK(hipStreamSynchronize(st));
+    if (r->h_status.get()[1].overflow) {
         gs2m_set_error("gs2m_rasterize_backward: the forward overflowed its instance arena (gs2m_raster_status / gs2m_raster_reserve, then run it again)");
         return 1;
     }
@@ -645,13 +560,13 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
         gs2m_set_error("gs2m_rasterize_backward: %llu instance rows exceed the 32-bit row offsets", n_rows);
         return 1;
     }
-    if (ensure(&r->d_bw_rows, &r->bw_rows_cap, (size_t)(n_rows ? n_rows : 1ull) * GS2M_BW_ROW)) return 1;
+    if (r->d_bw_rows.reserve((size_t)(n_rows ? n_rows : 1ull) * GS2M_BW_ROW)) return 1;
     r->bw_last_rows = n_rows;
     if (n_rows) {
         // rows no wave writes (instances behind every pixel's last contributor, tiles a cull level dropped) must read as zero
-        HIPCHK(hipMemsetAsync(r->d_bw_rows, 0, sizeof(float) * (size_t)n_rows * GS2M_BW_ROW, st));
-        gs2m_launch_blend_backward(st, gx, gy, r->d_keys, r->d_tile_start, recs, r->d_cams, P, r->last_cap, dL_dpix, r->d_bw_offset,
-                                   r->d_bw_rows, n_rows);
+        GS2M_HIPCHK(hipMemsetAsync(r->d_bw_rows.get(), 0, sizeof(float) * (size_t)n_rows * GS2M_BW_ROW, st));
+        gs2m_launch_blend_backward(st, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, r->d_cams.get(), P, r->last_cap, dL_dpix, r->d_bw_offset.get(),
+                                   r->d_bw_rows.get(), n_rows);
         if (dbg_check(r, st, "blend backward")) return 1;
     }
     GaussIn g;
@@ -680,7 +595,7 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
     o.dL_dsh = shs ? dL_dsh : nullptr;
     o.dL_dscale = dL_dscale;
     o.dL_drot = dL_drot;
-    gs2m_launch_gaussian_backward(st, g, r->d_cams, recs, r->d_bw_offset, r->d_bw_rows, n_rows, o);
+    gs2m_launch_gaussian_backward(st, g, r->d_cams.get(), recs, r->d_bw_offset.get(), r->d_bw_rows.get(), n_rows, o);
     if (dbg_check(r, st, "gaussian backward")) return 1;
     return 0;
 }
@@ -691,7 +606,7 @@ extern "C" int gs2m_raster_backward_rows(gs2m_raster* r, int64_t* rows, int64_t*
         return 1;
     }
     if (rows) *rows = (int64_t)r->bw_last_rows;
-    if (arena_bytes) *arena_bytes = r->d_bw_rows ? (int64_t)(r->bw_rows_cap * sizeof(float)) : 0;
+    if (arena_bytes) *arena_bytes = (int64_t)(r->d_bw_rows.capacity() * sizeof(float));
     return 0;
 }
 
@@ -719,7 +634,7 @@ extern "C" int gs2m_render_views(gs2m_raster* r, const gs2m_gaussians* gs, const
         return 1;
     }
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(r->device));
+    GS2M_HIPCHK(hipSetDevice(r->device));
     const int W = cams[0].width, H = cams[0].height;
     for (int v = 0; v < n_views; ++v)
         if (cams[v].width != W || cams[v].height != H || W <= 0 || H <= 0) {
@@ -734,9 +649,9 @@ extern "C" int gs2m_render_views(gs2m_raster* r, const gs2m_gaussians* gs, const
     r->fw_valid = false;   // the arenas now hold a multi-view pass: no gs2m_rasterize_backward on it
     const size_t img = (size_t)W * H;
     if (gs->P == 0) {
-        if (out_color) HIPCHK(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * img * n_views, st));
-        if (out_rgb8) HIPCHK(hipMemsetAsync(out_rgb8, 0, 3 * img * n_views, st));
-        HIPCHK(hipMemsetAsync(r->h_status + 1, 0, sizeof(ViewStatus) * n_views, st));
+        if (out_color) GS2M_HIPCHK(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * img * n_views, st));
+        if (out_rgb8) GS2M_HIPCHK(hipMemsetAsync(out_rgb8, 0, 3 * img * n_views, st));
+        GS2M_HIPCHK(hipMemsetAsync(r->h_status.get() + 1, 0, sizeof(ViewStatus) * n_views, st));
         return 0;
     }
     if (!gs->xyz || !gs->scales || !gs->rotations || !gs->opacities || !gs->shs) {
@@ -751,7 +666,7 @@ extern "C" int gs2m_render_views(gs2m_raster* r, const gs2m_gaussians* gs, const
     g.shs = gs->shs;
     g.shs_rest = gs->shs_rest;
     g.shs_packed = (r->pack_src == gs->shs && r->pack_src_rest == gs->shs_rest && r->pack_P == gs->P && gs->M == 16)
-                       ? r->d_shpack : nullptr;
+                       ? r->d_shpack.get() : nullptr;
     g.cov3D_precomp = nullptr;
     g.colors_precomp = nullptr;
     g.ids = nullptr;
@@ -760,12 +675,12 @@ extern "C" int gs2m_render_views(gs2m_raster* r, const gs2m_gaussians* gs, const
         r->model_src[2] == gs->rotations && r->model_src[3] == gs->opacities) {
         // the spatially ordered packed copy of THESE Gaussians (gs2m_raster_pack_model): every stage works on positions of
         // the copy; ids only enter the sort keys (tie order of the reference) and the radii output
-        g.xyz = r->d_pk_xyz;
-        g.scales = r->d_pk_scales;
-        g.rots = r->d_pk_rots;
-        g.opac = r->d_pk_opac;
-        g.ids = r->d_order;
-        r->run_rank = r->d_rank;
+        g.xyz = r->d_pk_xyz.get();
+        g.scales = r->d_pk_scales.get();
+        g.rots = r->d_pk_rots.get();
+        g.opac = r->d_pk_opac.get();
+        g.ids = r->d_order.get();
+        r->run_rank = r->d_rank.get();
     }
     g.P = gs->P;
     g.D = gs->sh_degree;
@@ -825,34 +740,34 @@ static int pack_common(gs2m_raster* r, const gs2m_gaussians* gs, const int32_t* 
     r->pack_P = 0;
     r->model_packed = false;
     if (gs->P <= 0 || gs->M != 16 || !gs->shs) return 0;  // nothing to pack: the kernels read the caller's layout
-    HIPCHK(hipSetDevice(r->device));
+    GS2M_HIPCHK(hipSetDevice(r->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t P = (size_t)gs->P;
     const size_t groups = (P + 63) / 64;
-    if (ensure(&r->d_shpack, &r->shpack_cap, groups * 12 * 64 * 4)) return 1;
+    if (r->d_shpack.reserve(groups * 12 * 64 * 4)) return 1;
     if (order) {
         if (!gs->xyz || !gs->scales || !gs->rotations || !gs->opacities) {
             gs2m_set_error("%s: NULL Gaussian array", who);
             return 1;
         }
-        if (ensure(&r->d_pk_xyz, &r->pk_cap3, 3 * P) || ensure(&r->d_pk_scales, &r->pk_cap3s, 3 * P) ||
-            ensure(&r->d_pk_rots, &r->pk_cap4, 4 * P) || ensure(&r->d_pk_opac, &r->pk_cap1, P) ||
-            ensure(&r->d_order, &r->order_cap, P) || ensure(&r->d_rank, &r->rank_cap, P + 1))
+        if (r->d_pk_xyz.reserve(3 * P) || r->d_pk_scales.reserve(3 * P) ||
+            r->d_pk_rots.reserve(4 * P) || r->d_pk_opac.reserve(P) ||
+            r->d_order.reserve(P) || r->d_rank.reserve(P + 1))
             return 1;
-        HIPCHK(hipMemcpyAsync(r->d_order, order, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemsetAsync(r->d_rank, 0xff, sizeof(int) * P, st));          // holes = -1
-        HIPCHK(hipMemsetAsync(r->d_rank + P, 0, sizeof(int), st));             // word P: "not a permutation" flag
-        gs2m_launch_pack_model(st, gs->P, r->d_order, gs->xyz, gs->scales, gs->rotations, gs->opacities, r->d_pk_xyz,
-                               r->d_pk_scales, r->d_pk_rots, r->d_pk_opac, r->d_rank, reinterpret_cast<unsigned*>(r->d_rank + P));
+        GS2M_HIPCHK(hipMemcpyAsync(r->d_order.get(), order, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+        GS2M_HIPCHK(hipMemsetAsync(r->d_rank.get(), 0xff, sizeof(int) * P, st));          // holes = -1
+        GS2M_HIPCHK(hipMemsetAsync(r->d_rank.get() + P, 0, sizeof(int), st));             // word P: "not a permutation" flag
+        gs2m_launch_pack_model(st, gs->P, r->d_order.get(), gs->xyz, gs->scales, gs->rotations, gs->opacities, r->d_pk_xyz.get(),
+                               r->d_pk_scales.get(), r->d_pk_rots.get(), r->d_pk_opac.get(), r->d_rank.get(), reinterpret_cast<unsigned*>(r->d_rank.get() + P));
         int bad = 0;
-        HIPCHK(hipMemcpyAsync(&bad, r->d_rank + P, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));   // one-time preparation: a checked result is worth the sync
+        GS2M_HIPCHK(hipMemcpyAsync(&bad, r->d_rank.get() + P, sizeof(int), hipMemcpyDeviceToHost, st));
+        GS2M_HIPCHK(hipStreamSynchronize(st));   // one-time preparation: a checked result is worth the sync
         if (bad) {
             gs2m_set_error("%s: order is not a permutation of 0..P-1", who);
             return 1;
         }
     }
-    gs2m_launch_pack_sh(st, gs->P, gs->shs, gs->shs_rest, r->d_shpack, order ? r->d_order : nullptr);
+    gs2m_launch_pack_sh(st, gs->P, gs->shs, gs->shs_rest, r->d_shpack.get(), order ? r->d_order.get() : nullptr);
     r->pack_src = gs->shs;
     r->pack_src_rest = gs->shs_rest;
     r->pack_P = gs->P;
@@ -896,26 +811,27 @@ extern "C" int gs2m_raster_status(gs2m_raster* r, gs2m_stream stream, int n_view
         gs2m_set_error("null handle");
         return 1;
     }
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(r->h_status, r->d_status, sizeof(ViewStatus), hipMemcpyDeviceToHost));   // the sticky word (the stream is idle)
+    GS2M_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    GS2M_HIPCHK(hipGetLastError());
+    ViewStatus* hs = r->h_status.get();
+    GS2M_HIPCHK(hipMemcpy(hs, r->d_status.get(), sizeof(ViewStatus), hipMemcpyDeviceToHost));   // the sticky word (the stream is idle)
     // slot 0 is sticky: an overflow in ANY call since the last query is reported (a later call on the same handle that
     // fits does not erase it), with the largest instance count any of those calls needed
-    int ov = r->h_status[0].overflow != 0;
-    int64_t req = r->h_status[0].num_rendered;
+    int ov = hs[0].overflow != 0;
+    int64_t req = hs[0].num_rendered;
     const int n = n_views < r->last_views_total ? n_views : r->last_views_total;
     for (int v = 0; v < r->last_views_total && v < GS2M_MAX_STATUS; ++v) {
-        ov |= r->h_status[1 + v].overflow != 0;
-        if ((int64_t)r->h_status[1 + v].num_rendered > req) req = r->h_status[1 + v].num_rendered;
+        ov |= hs[1 + v].overflow != 0;
+        if ((int64_t)hs[1 + v].num_rendered > req) req = hs[1 + v].num_rendered;
     }
-    for (int v = 0; v < n && num_rendered; ++v) num_rendered[v] = r->h_status[1 + v].num_rendered;
+    for (int v = 0; v < n && num_rendered; ++v) num_rendered[v] = hs[1 + v].num_rendered;
     if (overflow) *overflow = ov;
     if (required) *required = req;
     // the query consumes the sticky word (the stream is idle here)
-    HIPCHK(hipMemsetAsync(r->d_status, 0, sizeof(ViewStatus), (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    r->h_status[0].overflow = 0;
-    r->h_status[0].num_rendered = 0;
+    GS2M_HIPCHK(hipMemsetAsync(r->d_status.get(), 0, sizeof(ViewStatus), (hipStream_t)stream));
+    GS2M_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    hs[0].overflow = 0;
+    hs[0].num_rendered = 0;
     return 0;
 }
 
@@ -924,17 +840,8 @@ extern "C" int gs2m_raster_stage_times(gs2m_raster* r, gs2m_stream stream, doubl
         gs2m_set_error("gs2m_raster_stage_times: NULL argument");
         return 1;
     }
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    for (auto& p : r->ev_live) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess && p.stage >= 0 && p.stage < GS2M_N_STAGES) {
-            total_ms[p.stage] += ms;
-            launches[p.stage] += 1;
-        }
-        r->ev_free.push_back(p.a);
-        r->ev_free.push_back(p.b);
-    }
-    r->ev_live.clear();
+    GS2M_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    r->events.drain(total_ms, launches, GS2M_N_STAGES);
     return 0;
 }
 
@@ -944,11 +851,11 @@ extern "C" int gs2m_raster_blend_cycles(gs2m_raster* r, gs2m_stream stream, uint
         return 1;
     }
     for (int i = 0; i < GS2M_BLEND_PROF_COUNTERS; ++i) counters[i] = 0;
-    if (!r->d_blend_prof) return 0;
+    if (!r->d_blend_prof.get()) return 0;
     unsigned long long h[64 * 16];
-    HIPCHK(hipMemcpyAsync(h, r->d_blend_prof, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipMemsetAsync(r->d_blend_prof, 0, sizeof(h), (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    GS2M_HIPCHK(hipMemcpyAsync(h, r->d_blend_prof.get(), sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    GS2M_HIPCHK(hipMemsetAsync(r->d_blend_prof.get(), 0, sizeof(h), (hipStream_t)stream));
+    GS2M_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     for (int c = 0; c < 64; ++c)
         for (int i = 0; i < GS2M_BLEND_PROF_COUNTERS; ++i) counters[i] += h[c * 16 + i];
     return 0;
@@ -961,7 +868,7 @@ extern "C" int gs2m_raster_download_geometry(gs2m_raster* r, gs2m_stream stream,
         gs2m_set_error("gs2m_raster_download_geometry: view %d / P %d do not match the last call", v, P);
         return 1;
     }
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    GS2M_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     if (P == 0) return 0;
     GeomRec* h = (GeomRec*)malloc(sizeof(GeomRec) * (size_t)P);
     float4* hab = (float4*)malloc(sizeof(float4) * 2 * (size_t)P);
@@ -974,9 +881,9 @@ extern "C" int gs2m_raster_download_geometry(gs2m_raster* r, gs2m_stream stream,
         return 1;
     }
     // the two arrays of the last pass (GeomRecs: [last_nv * P] 32-B parts, then the 16-B parts) -> whole records
-    hipError_t e = hipMemcpy(hab, r->d_recs + 2 * (size_t)v * P, sizeof(float4) * 2 * (size_t)P, hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(hab, r->d_recs.get() + 2 * (size_t)v * P, sizeof(float4) * 2 * (size_t)P, hipMemcpyDeviceToHost);
     if (e == hipSuccess)
-        e = hipMemcpy(hc, r->d_recs + 2 * (size_t)r->last_nv * P + (size_t)v * P, sizeof(float4) * (size_t)P, hipMemcpyDeviceToHost);
+        e = hipMemcpy(hc, r->d_recs.get() + 2 * (size_t)r->last_nv * P + (size_t)v * P, sizeof(float4) * (size_t)P, hipMemcpyDeviceToHost);
     for (int i = 0; e == hipSuccess && i < P; ++i) {
         memcpy(&h[i], &hab[2 * (size_t)i], 32);
         memcpy(reinterpret_cast<char*>(&h[i]) + 32, &hc[i], 16);
@@ -991,7 +898,7 @@ extern "C" int gs2m_raster_download_geometry(gs2m_raster* r, gs2m_stream stream,
     int* ord = nullptr;   // packed model: record position -> Gaussian id (the taps are indexed by id, like the reference's arrays)
     if (r->last_packed) {
         ord = (int*)malloc(sizeof(int) * (size_t)P);
-        if (!ord || hipMemcpy(ord, r->d_order, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost) != hipSuccess) {
+        if (!ord || hipMemcpy(ord, r->d_order.get(), sizeof(int) * (size_t)P, hipMemcpyDeviceToHost) != hipSuccess) {
             free(ord);
             free(h);
             gs2m_set_error("gs2m_raster_download_geometry: cannot read the packed order");
@@ -1038,10 +945,10 @@ extern "C" int gs2m_raster_download_binning(gs2m_raster* r, gs2m_stream stream, 
         gs2m_set_error("gs2m_raster_download_binning: arguments do not match the last call");
         return 1;
     }
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    GS2M_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     if (ranges) {
         unsigned* ts = (unsigned*)malloc(sizeof(unsigned) * (size_t)(n_tiles + 1));
-        HIPCHK(hipMemcpy(ts, r->d_tile_start + (size_t)v * (n_tiles + 1), sizeof(unsigned) * (size_t)(n_tiles + 1),
+        GS2M_HIPCHK(hipMemcpy(ts, r->d_tile_start.get() + (size_t)v * (n_tiles + 1), sizeof(unsigned) * (size_t)(n_tiles + 1),
                          hipMemcpyDeviceToHost));
         for (int t = 0; t < n_tiles; ++t) {
             // the reference leaves {0,0} for empty tiles (cudaMemset, rasterizer_impl.cu:310)
@@ -1054,7 +961,7 @@ extern "C" int gs2m_raster_download_binning(gs2m_raster* r, gs2m_stream stream, 
     if (point_list && n > 0) {
         if ((uint64_t)n > r->last_cap) n = r->last_cap;
         unsigned long long* k = (unsigned long long*)malloc(sizeof(unsigned long long) * (size_t)n);
-        HIPCHK(hipMemcpy(k, r->d_keys + (size_t)v * r->last_cap, sizeof(unsigned long long) * (size_t)n,
+        GS2M_HIPCHK(hipMemcpy(k, r->d_keys.get() + (size_t)v * r->last_cap, sizeof(unsigned long long) * (size_t)n,
                          hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < n; ++i) point_list[i] = (uint32_t)(k[i] & 0xffffffffull);
         free(k);

@@ -8,66 +8,50 @@
 #include <vector>
 
 #include "../../include/gs2mesh_amd.h"
+#include "device_memory.h"
 #include "tsdf_common.h"
 #include "tsdf_internal.h"
 #include "roctx_ranges.h"
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e__ = (expr);                                                              \
-        if (e__ != hipSuccess) {                                                              \
-            gs2m_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
 
 struct gs2m_tsdf {
     int device = 0;
     double voxel_length = 0, sdf_trunc = 0, unit_length = 0;
     int color_type = 1, resolution = 16, stride = 4;
-    TsdfVolume V;
+    TsdfVolume V;           // what the kernels get, by value: the pointers of `vol` below and the sizes, filled once at creation
+    struct {                // owners of V's arrays (sizes: tsdf_common.h)
+        DeviceBuffer<float> tsdf, weight;
+        DeviceBuffer<unsigned> rgb, stamp, touched, counters;
+        DeviceBuffer<int> block_keys, hash_vals;
+        DeviceBuffer<unsigned char> halo;
+        DeviceBuffer<unsigned long long> hash_keys, fmask, totals;
+    } vol;
     unsigned frame_id = 0;  // monotonic, never reset (stamps of old frames can never alias)
-    unsigned* h_counters = nullptr;         // pinned [4]
-    unsigned long long* h_totals = nullptr; // pinned [1]
+    PinnedBuffer<unsigned> h_counters;           // [4]
+    PinnedBuffer<unsigned long long> h_totals;   // [1]
     int n_cu = 256;
-    McDevTables* d_mc = nullptr;          // marching-cubes case table (generated at create)
-    unsigned* d_blk_tris = nullptr;       // [max_blocks] per-block triangle counts / offsets
-    unsigned long long* d_ntri = nullptr; // [1]
-    // the last mesh gs2m_tsdf_extract_mesh produced, welded, on the device (read with gs2m_tsdf_mesh_copy)
-    double* mesh_v = nullptr;      // [mesh_nv][3]
-    double* mesh_c = nullptr;      // [mesh_nv][3]
-    int* mesh_e = nullptr;         // [mesh_nv][4]
-    int* mesh_tri = nullptr;       // [mesh_nt][3]
+    DeviceBuffer<unsigned char> d_mc;            // marching-cubes case table (McDevTables, generated at create)
+    const McDevTables* mc() const { return reinterpret_cast<const McDevTables*>(d_mc.get()); }
+    DeviceBuffer<unsigned> d_blk_tris;           // [max_blocks] per-block triangle counts / offsets
+    DeviceBuffer<unsigned long long> d_ntri;     // [1]
+    // the last mesh gs2m_tsdf_extract_mesh produced, welded, on the device (read with gs2m_tsdf_mesh_copy); grow-only
+    DeviceBuffer<double> mesh_v, mesh_c;   // [mesh_nv][3]
+    DeviceBuffer<int> mesh_e;              // [mesh_nv][4]
+    DeviceBuffer<int> mesh_tri;            // [mesh_nt][3]
     int64_t mesh_nv = 0, mesh_nt = 0;
-    size_t mesh_cap_v = 0, mesh_cap_t = 0;   // capacities (vertices / triangles) of the cached-mesh arrays: grow-only
-    char* mesh_scratch = nullptr;            // grow-only arena of the extraction's temporaries (soup, weld table, scan)
-    size_t mesh_scratch_cap = 0;
+    ScratchArena mesh_scratch;             // the extraction's temporaries (soup, weld table, scan)
     int timing = 0;
-    struct EvPair {
-        int stage;
-        hipEvent_t a, b;
-        int frames;   // frames the timed launch covered (a batch counts as that many launches)
-    };
-    std::vector<EvPair> ev_live;
-    std::vector<hipEvent_t> ev_free;
-    TsdfBatchFrame* d_bframes = nullptr;   // [GS2M_TSDF_MAX_BATCH] frame descriptors of the batch in flight
+    EventPool events;                      // weight = frames the timed launch covered (a batch counts as that many launches)
+    DeviceBuffer<TsdfBatchFrame> d_bframes;   // [GS2M_TSDF_MAX_BATCH] frame descriptors of the batch in flight
     // pinned staging ring for the descriptors (a pageable source would make the "async" copy wait for the stream)
     static const int kRing = 8;
-    TsdfBatchFrame* h_bframes = nullptr;   // [kRing][GS2M_TSDF_MAX_BATCH]
+    PinnedBuffer<TsdfBatchFrame> h_bframes;   // [kRing][GS2M_TSDF_MAX_BATCH]
     hipEvent_t ring_done[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     unsigned ring_next = 0;
-};
-
-static hipEvent_t tsdf_ev_get(gs2m_tsdf* t) {
-    if (!t->ev_free.empty()) {
-        hipEvent_t e = t->ev_free.back();
-        t->ev_free.pop_back();
-        return e;
+    ~gs2m_tsdf() {
+        for (auto e : ring_done)
+            if (e) (void)hipEventDestroy(e);
     }
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
+};
 
 // General 4x4 inverse (cofactors), double.  The reference hands Open3D world->camera and
 // Open3D inverts it again (PointCloudFactory.cpp: camera_pose = extrinsic.inverse()).
@@ -96,25 +80,69 @@ static bool invert4x4(const double* m, double* inv) {
     return true;
 }
 
-// `whole_pool`: at creation (hipMalloc'ed memory is not zero); later resets only clear the slots that were handed out
+// `whole_pool`: at creation (fresh device memory is not zero); later resets only clear the slots that were handed out
 static int zero_state(gs2m_tsdf* t, hipStream_t st, bool whole_pool, long long keep_first = -1) {
     TsdfVolume& V = t->V;
     if (whole_pool) {
-        HIPCHK(hipMemsetAsync(V.tsdf, 0, sizeof(float) * (size_t)V.max_blocks * GS2M_TSDF_VOX, st));
-        HIPCHK(hipMemsetAsync(V.weight, 0, sizeof(float) * (size_t)V.max_blocks * GS2M_TSDF_VOX, st));
-        if (V.rgb) HIPCHK(hipMemsetAsync(V.rgb, 0, sizeof(unsigned) * 3 * (size_t)V.max_blocks * GS2M_TSDF_VOX, st));
-        HIPCHK(hipMemsetAsync(V.halo, 0, (size_t)V.max_blocks, st));
+        GS2M_HIPCHK(hipMemsetAsync(V.tsdf, 0, sizeof(float) * (size_t)V.max_blocks * GS2M_TSDF_VOX, st));
+        GS2M_HIPCHK(hipMemsetAsync(V.weight, 0, sizeof(float) * (size_t)V.max_blocks * GS2M_TSDF_VOX, st));
+        if (V.rgb) GS2M_HIPCHK(hipMemsetAsync(V.rgb, 0, sizeof(unsigned) * 3 * (size_t)V.max_blocks * GS2M_TSDF_VOX, st));
+        GS2M_HIPCHK(hipMemsetAsync(V.halo, 0, (size_t)V.max_blocks, st));
     } else if (keep_first < 0) {
         gs2m_launch_tsdf_clear_used(st, V);   // reads counters[0] on the device: no host sync
     } else {
         gs2m_launch_tsdf_clear_from(st, V, (unsigned)keep_first);   // gs2m_tsdf_replace: slots [0, keep_first) are overwritten next
     }
-    HIPCHK(hipMemsetAsync(V.hash_keys, 0xff, sizeof(unsigned long long) * (size_t)V.hash_cap, st));
-    HIPCHK(hipMemsetAsync(V.hash_vals, 0xff, sizeof(int) * (size_t)V.hash_cap, st));
-    HIPCHK(hipMemsetAsync(V.stamp, 0, sizeof(unsigned) * (size_t)V.hash_cap, st));
-    HIPCHK(hipMemsetAsync(V.fmask, 0, sizeof(unsigned long long) * (size_t)V.hash_cap, st));
-    HIPCHK(hipMemsetAsync(V.counters, 0, sizeof(unsigned) * 4, st));
-    HIPCHK(hipMemsetAsync(V.totals, 0, sizeof(unsigned long long), st));
+    GS2M_HIPCHK(hipMemsetAsync(V.hash_keys, 0xff, sizeof(unsigned long long) * (size_t)V.hash_cap, st));
+    GS2M_HIPCHK(hipMemsetAsync(V.hash_vals, 0xff, sizeof(int) * (size_t)V.hash_cap, st));
+    GS2M_HIPCHK(hipMemsetAsync(V.stamp, 0, sizeof(unsigned) * (size_t)V.hash_cap, st));
+    GS2M_HIPCHK(hipMemsetAsync(V.fmask, 0, sizeof(unsigned long long) * (size_t)V.hash_cap, st));
+    GS2M_HIPCHK(hipMemsetAsync(V.counters, 0, sizeof(unsigned) * 4, st));
+    GS2M_HIPCHK(hipMemsetAsync(V.totals, 0, sizeof(unsigned long long), st));
+    return 0;
+}
+
+// allocates and clears the volume of a new handle, whose scalar fields are set; on failure the caller deletes the handle
+static int init_volume(gs2m_tsdf* t, int64_t max_blocks) {
+    memset(&t->V, 0, sizeof(t->V));
+    TsdfVolume& V = t->V;
+    V.max_blocks = (unsigned)max_blocks;
+    unsigned cap = 1024;
+    while ((uint64_t)cap < 2ull * (uint64_t)max_blocks) cap <<= 1;
+    V.hash_cap = cap;
+    V.has_color = t->color_type == GS2M_TSDF_COLOR_RGB8;
+    const size_t nvox = (size_t)max_blocks * GS2M_TSDF_VOX, nb = (size_t)max_blocks;
+    auto& o = t->vol;
+    if (o.tsdf.reserve_exact(nvox) || o.weight.reserve_exact(nvox) || (V.has_color && o.rgb.reserve_exact(3 * nvox)) ||
+        o.block_keys.reserve_exact(3 * nb) || o.halo.reserve_exact(nb) || o.hash_keys.reserve_exact(cap) ||
+        o.hash_vals.reserve_exact(cap) || o.stamp.reserve_exact(cap) || o.touched.reserve_exact(cap) || o.fmask.reserve_exact(cap) ||
+        t->d_bframes.reserve_exact(GS2M_TSDF_MAX_BATCH) || t->h_bframes.reserve(GS2M_TSDF_MAX_BATCH * gs2m_tsdf::kRing) ||
+        o.counters.reserve_exact(4) || o.totals.reserve_exact(1) || t->d_mc.reserve_exact(gs2m_mc_tables_bytes()) ||
+        t->d_blk_tris.reserve_exact(nb) || t->d_ntri.reserve_exact(1) || t->h_counters.reserve(4) || t->h_totals.reserve(1)) {
+        gs2m_set_error("gs2m_tsdf_create: out of device memory for %lld blocks (%.1f MiB)", (long long)max_blocks,
+                       (double)nvox * 20.0 / 1048576.0);
+        return 1;
+    }
+    V.tsdf = o.tsdf.get();
+    V.weight = o.weight.get();
+    V.rgb = o.rgb.get();   // null without colour
+    V.block_keys = o.block_keys.get();
+    V.halo = o.halo.get();
+    V.hash_keys = o.hash_keys.get();
+    V.hash_vals = o.hash_vals.get();
+    V.stamp = o.stamp.get();
+    V.touched = o.touched.get();
+    V.fmask = o.fmask.get();
+    V.counters = o.counters.get();
+    V.totals = o.totals.get();
+    std::vector<unsigned char> tab(gs2m_mc_tables_bytes());
+    if (!gs2m_mc_tables_fill(tab.data()) ||
+        hipMemcpy(t->d_mc.get(), tab.data(), tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        gs2m_set_error("gs2m_tsdf_create: marching-cubes table generation failed");
+        return 1;
+    }
+    if (zero_state(t, (hipStream_t)0, true)) return 1;
+    GS2M_HIPCHK(hipStreamSynchronize((hipStream_t)0));
     return 0;
 }
 
@@ -135,7 +163,7 @@ extern "C" int gs2m_tsdf_create(gs2m_tsdf** out, double voxel_length, double sdf
         gs2m_set_error("gs2m_tsdf_create: bad argument");
         return 1;
     }
-    HIPCHK(hipSetDevice(device));
+    GS2M_HIPCHK(hipSetDevice(device));
     gs2m_tsdf* t = new gs2m_tsdf();
     t->device = device;
     t->voxel_length = voxel_length;
@@ -143,92 +171,16 @@ extern "C" int gs2m_tsdf_create(gs2m_tsdf** out, double voxel_length, double sdf
     t->unit_length = voxel_length * volume_unit_resolution;  // ScalableTSDFVolume ctor
     t->color_type = color_type;
     t->stride = depth_sampling_stride;
-    memset(&t->V, 0, sizeof(t->V));
-    TsdfVolume& V = t->V;
-    V.max_blocks = (unsigned)max_blocks;
-    unsigned cap = 1024;
-    while ((uint64_t)cap < 2ull * (uint64_t)max_blocks) cap <<= 1;
-    V.hash_cap = cap;
-    V.has_color = color_type == GS2M_TSDF_COLOR_RGB8;
-    const size_t nvox = (size_t)max_blocks * GS2M_TSDF_VOX;
-    bool ok = hipMalloc((void**)&V.tsdf, sizeof(float) * nvox) == hipSuccess &&
-              hipMalloc((void**)&V.weight, sizeof(float) * nvox) == hipSuccess &&
-              (!V.has_color || hipMalloc((void**)&V.rgb, sizeof(unsigned) * 3 * nvox) == hipSuccess) &&
-              hipMalloc((void**)&V.block_keys, sizeof(int) * 3 * (size_t)max_blocks) == hipSuccess &&
-              hipMalloc((void**)&V.halo, (size_t)max_blocks) == hipSuccess &&
-              hipMalloc((void**)&V.hash_keys, sizeof(unsigned long long) * (size_t)cap) == hipSuccess &&
-              hipMalloc((void**)&V.hash_vals, sizeof(int) * (size_t)cap) == hipSuccess &&
-              hipMalloc((void**)&V.stamp, sizeof(unsigned) * (size_t)cap) == hipSuccess &&
-              hipMalloc((void**)&V.touched, sizeof(unsigned) * (size_t)cap) == hipSuccess &&
-              hipMalloc((void**)&V.fmask, sizeof(unsigned long long) * (size_t)cap) == hipSuccess &&
-              hipMalloc((void**)&t->d_bframes, sizeof(TsdfBatchFrame) * GS2M_TSDF_MAX_BATCH) == hipSuccess &&
-              hipHostMalloc((void**)&t->h_bframes, sizeof(TsdfBatchFrame) * GS2M_TSDF_MAX_BATCH * gs2m_tsdf::kRing) == hipSuccess &&
-              hipMalloc((void**)&V.counters, sizeof(unsigned) * 4) == hipSuccess &&
-              hipMalloc((void**)&V.totals, sizeof(unsigned long long)) == hipSuccess &&
-              hipMalloc((void**)&t->d_mc, gs2m_mc_tables_bytes()) == hipSuccess &&
-              hipMalloc((void**)&t->d_blk_tris, sizeof(unsigned) * (size_t)max_blocks) == hipSuccess &&
-              hipMalloc((void**)&t->d_ntri, sizeof(unsigned long long)) == hipSuccess &&
-              hipHostMalloc((void**)&t->h_counters, sizeof(unsigned) * 4) == hipSuccess &&
-              hipHostMalloc((void**)&t->h_totals, sizeof(unsigned long long)) == hipSuccess;
-    if (!ok) {
-        gs2m_set_error("gs2m_tsdf_create: out of device memory for %lld blocks (%.1f MiB)", (long long)max_blocks,
-                       (double)nvox * 20.0 / 1048576.0);
-        gs2m_tsdf_destroy(t);
+    if (init_volume(t, max_blocks)) {
+        delete t;
         return 1;
     }
-    {
-        std::vector<unsigned char> tab(gs2m_mc_tables_bytes());
-        if (!gs2m_mc_tables_fill(tab.data()) ||
-            hipMemcpy(t->d_mc, tab.data(), tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            gs2m_set_error("gs2m_tsdf_create: marching-cubes table generation failed");
-            gs2m_tsdf_destroy(t);
-            return 1;
-        }
-    }
-    if (zero_state(t, (hipStream_t)0, true)) {
-        gs2m_tsdf_destroy(t);
-        return 1;
-    }
-    HIPCHK(hipStreamSynchronize((hipStream_t)0));
     *out = t;
     return 0;
 }
 
 extern "C" int gs2m_tsdf_destroy(gs2m_tsdf* t) {
-    if (!t) return 0;
-    TsdfVolume& V = t->V;
-    (void)hipFree(V.tsdf);
-    (void)hipFree(V.weight);
-    (void)hipFree(V.rgb);
-    (void)hipFree(V.block_keys);
-    (void)hipFree(V.halo);
-    (void)hipFree(V.hash_keys);
-    (void)hipFree(V.hash_vals);
-    (void)hipFree(V.stamp);
-    (void)hipFree(V.touched);
-    (void)hipFree(V.fmask);
-    (void)hipFree(t->d_bframes);
-    (void)hipHostFree(t->h_bframes);
-    for (auto e : t->ring_done)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipFree(V.counters);
-    (void)hipFree(V.totals);
-    (void)hipFree(t->d_mc);
-    (void)hipFree(t->d_blk_tris);
-    (void)hipFree(t->d_ntri);
-    (void)hipFree(t->mesh_scratch);
-    (void)hipFree(t->mesh_v);
-    (void)hipFree(t->mesh_c);
-    (void)hipFree(t->mesh_e);
-    (void)hipFree(t->mesh_tri);
-    (void)hipHostFree(t->h_counters);
-    (void)hipHostFree(t->h_totals);
-    for (auto& p : t->ev_live) {
-        (void)hipEventDestroy(p.a);
-        (void)hipEventDestroy(p.b);
-    }
-    for (auto e : t->ev_free) (void)hipEventDestroy(e);
-    delete t;
+    delete t;   // every buffer and event is a member
     return 0;
 }
 
@@ -237,7 +189,7 @@ extern "C" int gs2m_tsdf_reset(gs2m_tsdf* t, gs2m_stream stream) {
         gs2m_set_error("null handle");
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     return zero_state(t, (hipStream_t)stream, false);
 }
 
@@ -309,18 +261,18 @@ extern "C" int gs2m_tsdf_integrate(gs2m_tsdf* t, const float* depth, const uint8
         gs2m_set_error("gs2m_tsdf_integrate: bad intrinsics / size");
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
     TsdfFrame f;
     if (fill_frame(t, f, width, height, fx, fy, cx, cy, extrinsic_w2c, depth_scale, depth_trunc, min_depth, mask != nullptr))
         return 1;
-    HIPCHK(hipMemsetAsync(t->V.counters + 1, 0, sizeof(unsigned), st));  // touched_count = 0
+    GS2M_HIPCHK(hipMemsetAsync(t->V.counters + 1, 0, sizeof(unsigned), st));  // touched_count = 0
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
     if (t->timing) {
-        e0 = tsdf_ev_get(t);
-        e1 = tsdf_ev_get(t);
-        e2 = tsdf_ev_get(t);
-        e3 = tsdf_ev_get(t);
+        e0 = t->events.get();
+        e1 = t->events.get();
+        e2 = t->events.get();
+        e3 = t->events.get();
     }
     const bool tm = e0 && e1 && e2 && e3;
     if (tm) (void)hipEventRecord(e0, st);
@@ -339,8 +291,8 @@ extern "C" int gs2m_tsdf_integrate(gs2m_tsdf* t, const float* depth, const uint8
     }
     if (tm) {
         (void)hipEventRecord(e3, st);
-        t->ev_live.push_back({0, e0, e1, 1});
-        t->ev_live.push_back({1, e2, e3, 1});
+        t->events.push(0, e0, e1);
+        t->events.push(1, e2, e3);
     }
     return 0;
 }
@@ -361,15 +313,15 @@ extern "C" int gs2m_tsdf_integrate_batch(gs2m_tsdf* t, int n_frames, const float
         gs2m_set_error("gs2m_tsdf_integrate_batch: bad intrinsics / size (the sweep packs pixel coordinates in 16 bits: <= 65535)");
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
     for (int f0 = 0; f0 < n_frames; f0 += GS2M_TSDF_MAX_BATCH) {
         const int nf = n_frames - f0 < GS2M_TSDF_MAX_BATCH ? n_frames - f0 : GS2M_TSDF_MAX_BATCH;
         // next slot of the pinned staging ring; its previous copy (kRing batches ago) has long completed
         const unsigned slot = t->ring_next++ % gs2m_tsdf::kRing;
-        if (t->ring_done[slot]) HIPCHK(hipEventSynchronize(t->ring_done[slot]));
-        else HIPCHK(hipEventCreateWithFlags(&t->ring_done[slot], hipEventDisableTiming));
-        TsdfBatchFrame* hb = t->h_bframes + (size_t)slot * GS2M_TSDF_MAX_BATCH;
+        if (t->ring_done[slot]) GS2M_HIPCHK(hipEventSynchronize(t->ring_done[slot]));
+        else GS2M_HIPCHK(hipEventCreateWithFlags(&t->ring_done[slot], hipEventDisableTiming));
+        TsdfBatchFrame* hb = t->h_bframes.get() + (size_t)slot * GS2M_TSDF_MAX_BATCH;
         for (int k = 0; k < nf; ++k) {
             const int i = f0 + k;
             if (!depth[i] || (t->V.has_color && !color[i])) {
@@ -384,22 +336,22 @@ extern "C" int gs2m_tsdf_integrate_batch(gs2m_tsdf* t, int n_frames, const float
             hb[k].color = color ? color[i] : nullptr;
             hb[k].mask = m;
         }
-        HIPCHK(hipMemcpyAsync(t->d_bframes, hb, sizeof(TsdfBatchFrame) * nf, hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(t->ring_done[slot], st));
-        HIPCHK(hipMemsetAsync(t->V.counters + 1, 0, sizeof(unsigned), st));  // touched_count = 0
-        HIPCHK(hipMemsetAsync(t->V.counters + 3, 0, sizeof(unsigned), st));  // work counter of the batch sweep
+        GS2M_HIPCHK(hipMemcpyAsync(t->d_bframes.get(), hb, sizeof(TsdfBatchFrame) * nf, hipMemcpyHostToDevice, st));
+        GS2M_HIPCHK(hipEventRecord(t->ring_done[slot], st));
+        GS2M_HIPCHK(hipMemsetAsync(t->V.counters + 1, 0, sizeof(unsigned), st));  // touched_count = 0
+        GS2M_HIPCHK(hipMemsetAsync(t->V.counters + 3, 0, sizeof(unsigned), st));  // work counter of the batch sweep
         hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
         if (t->timing) {
-            e0 = tsdf_ev_get(t);
-            e1 = tsdf_ev_get(t);
-            e2 = tsdf_ev_get(t);
-            e3 = tsdf_ev_get(t);
+            e0 = t->events.get();
+            e1 = t->events.get();
+            e2 = t->events.get();
+            e3 = t->events.get();
         }
         const bool tm = e0 && e1 && e2 && e3;
         if (tm) (void)hipEventRecord(e0, st);
         {
             Gs2mRange rg("gs2m:tsdf_touch_batch");
-            gs2m_launch_tsdf_touch_batch(st, t->V, hb[0].f, nf, t->d_bframes);
+            gs2m_launch_tsdf_touch_batch(st, t->V, hb[0].f, nf, t->d_bframes.get());
         }
         if (tm) {
             (void)hipEventRecord(e1, st);
@@ -407,12 +359,12 @@ extern "C" int gs2m_tsdf_integrate_batch(gs2m_tsdf* t, int n_frames, const float
         }
         {
             Gs2mRange rg("gs2m:tsdf_integrate_batch");
-            gs2m_launch_tsdf_integrate_batch(st, t->n_cu, t->V, t->d_bframes);
+            gs2m_launch_tsdf_integrate_batch(st, t->n_cu, t->V, t->d_bframes.get());
         }
         if (tm) {
             (void)hipEventRecord(e3, st);
-            t->ev_live.push_back({0, e0, e1, nf});
-            t->ev_live.push_back({1, e2, e3, nf});
+            t->events.push(0, e0, e1, nf);
+            t->events.push(1, e2, e3, nf);
         }
     }
     return 0;
@@ -432,17 +384,8 @@ extern "C" int gs2m_tsdf_stage_times(gs2m_tsdf* t, gs2m_stream stream, double* t
         gs2m_set_error("gs2m_tsdf_stage_times: NULL argument");
         return 1;
     }
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    for (auto& p : t->ev_live) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess && (p.stage == 0 || p.stage == 1)) {
-            total_ms[p.stage] += ms;
-            launches[p.stage] += p.frames;   // a batch launch counts as its frames: averages stay per frame
-        }
-        t->ev_free.push_back(p.a);
-        t->ev_free.push_back(p.b);
-    }
-    t->ev_live.clear();
+    GS2M_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    t->events.drain(total_ms, launches, 2);   // a batch launch counts as its frames: averages stay per frame
     return 0;
 }
 
@@ -453,15 +396,15 @@ extern "C" int gs2m_tsdf_status(gs2m_tsdf* t, gs2m_stream stream, int64_t* n_blo
         return 1;
     }
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(t->h_counters, t->V.counters, sizeof(unsigned) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(t->h_totals, t->V.totals, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    unsigned nb = t->h_counters[0];
+    GS2M_HIPCHK(hipMemcpyAsync(t->h_counters.get(), t->V.counters, sizeof(unsigned) * 4, hipMemcpyDeviceToHost, st));
+    GS2M_HIPCHK(hipMemcpyAsync(t->h_totals.get(), t->V.totals, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    GS2M_HIPCHK(hipStreamSynchronize(st));
+    GS2M_HIPCHK(hipGetLastError());
+    unsigned nb = t->h_counters.get()[0];
     if (nb > t->V.max_blocks) nb = t->V.max_blocks;
     if (n_blocks) *n_blocks = nb;
-    if (block_updates) *block_updates = (int64_t)t->h_totals[0];
-    if (overflow) *overflow = (int)t->h_counters[2];
+    if (block_updates) *block_updates = (int64_t)t->h_totals.get()[0];
+    if (overflow) *overflow = (int)t->h_counters.get()[2];
     return 0;
 }
 
@@ -470,8 +413,8 @@ extern "C" int gs2m_tsdf_flags_device(gs2m_tsdf* t, uint32_t* flags_dev, gs2m_st
         gs2m_set_error("gs2m_tsdf_flags_device: NULL argument");
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(hipMemcpyAsync(flags_dev, t->V.counters + 2, sizeof(unsigned), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    GS2M_HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipMemcpyAsync(flags_dev, t->V.counters + 2, sizeof(unsigned), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
@@ -481,7 +424,7 @@ extern "C" int gs2m_tsdf_block_keys(gs2m_tsdf* t, int64_t n, int32_t* keys, gs2m
         return 1;
     }
     if (n == 0) return 0;
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     gs2m_launch_tsdf_owned_keys((hipStream_t)stream, (unsigned)n, t->V, keys);   // halo copies -> sentinel key
     return 0;
 }
@@ -517,12 +460,12 @@ extern "C" int gs2m_tsdf_block_map(gs2m_tsdf* t, const int32_t* lo, const int32_
         gs2m_set_error("gs2m_tsdf_block_map: bad argument");
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(cells, 0, (size_t)total, st));
+    GS2M_HIPCHK(hipMemsetAsync(cells, 0, (size_t)total, st));
     gs2m_launch_tsdf_block_map(st, t->V, lo, dim, cells, nc, (unsigned)flags, window_hash(lo, dim), rank, (unsigned)frames_local,
                                (unsigned)frames_base);
-    HIPCHK(hipGetLastError());
+    GS2M_HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -534,12 +477,12 @@ extern "C" int gs2m_tsdf_map_keys(gs2m_tsdf* t, const int32_t* lo, const int32_t
         gs2m_set_error("gs2m_tsdf_map_keys: bad argument");
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
     gs2m_launch_tsdf_map_keys(st, lo, dim, cells, nc, keys, (unsigned)(max_keys > 0x7fffffff ? 0x7fffffff : max_keys));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(header_host, cells + nc, (size_t)(total - nc), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    GS2M_HIPCHK(hipGetLastError());
+    GS2M_HIPCHK(hipMemcpyAsync(header_host, cells + nc, (size_t)(total - nc), hipMemcpyDeviceToHost, st));
+    GS2M_HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -554,7 +497,7 @@ extern "C" int gs2m_tsdf_download(gs2m_tsdf* t, gs2m_stream stream, int64_t n, i
     if (n > nb) n = nb;
     if (n == 0) return 0;
     const size_t nv = (size_t)n * GS2M_TSDF_VOX;
-    if (keys) HIPCHK(hipMemcpy(keys, t->V.block_keys, sizeof(int) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+    if (keys) GS2M_HIPCHK(hipMemcpy(keys, t->V.block_keys, sizeof(int) * 3 * (size_t)n, hipMemcpyDeviceToHost));
     std::vector<float> tmp;
     // device layout (4x4x4 micro-blocks, tsdf_common.h)  ->  Open3D IndexOf x*256 + y*16 + z
     auto reorder_f = [&](const float* src, float* dst) {
@@ -567,12 +510,12 @@ extern "C" int gs2m_tsdf_download(gs2m_tsdf* t, gs2m_stream stream, int64_t n, i
     };
     if (tsdf) {
         tmp.resize(nv);
-        HIPCHK(hipMemcpy(tmp.data(), t->V.tsdf, sizeof(float) * nv, hipMemcpyDeviceToHost));
+        GS2M_HIPCHK(hipMemcpy(tmp.data(), t->V.tsdf, sizeof(float) * nv, hipMemcpyDeviceToHost));
         reorder_f(tmp.data(), tsdf);
     }
     if (weight) {
         tmp.resize(nv);
-        HIPCHK(hipMemcpy(tmp.data(), t->V.weight, sizeof(float) * nv, hipMemcpyDeviceToHost));
+        GS2M_HIPCHK(hipMemcpy(tmp.data(), t->V.weight, sizeof(float) * nv, hipMemcpyDeviceToHost));
         reorder_f(tmp.data(), weight);
     }
     if (rgb_sum) {
@@ -580,7 +523,7 @@ extern "C" int gs2m_tsdf_download(gs2m_tsdf* t, gs2m_stream stream, int64_t n, i
             memset(rgb_sum, 0, sizeof(uint32_t) * 3 * nv);
         } else {
             std::vector<unsigned> c(3 * nv);
-            HIPCHK(hipMemcpy(c.data(), t->V.rgb, sizeof(unsigned) * 3 * nv, hipMemcpyDeviceToHost));
+            GS2M_HIPCHK(hipMemcpy(c.data(), t->V.rgb, sizeof(unsigned) * 3 * nv, hipMemcpyDeviceToHost));
             for (int64_t b = 0; b < n; ++b)
                 for (int ch = 0; ch < 3; ++ch)
                     for (int z = 0; z < 16; ++z)
@@ -600,7 +543,7 @@ extern "C" int gs2m_tsdf_pack(gs2m_tsdf* t, const int32_t* keys, int64_t n, int 
         return 1;
     }
     if (n == 0) return 0;
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     gs2m_launch_tsdf_pack((hipStream_t)stream, (unsigned)n, t->V, keys, form, buf_f32, (long long*)buf_i64);
     return 0;
 }
@@ -612,7 +555,7 @@ extern "C" int gs2m_tsdf_unpack(gs2m_tsdf* t, const int32_t* keys, int64_t n, in
         return 1;
     }
     if (n == 0) return 0;
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     gs2m_launch_tsdf_unpack((hipStream_t)stream, (unsigned)n, t->V, keys, form, buf_f32, (const long long*)buf_i64, halo);
     return 0;
 }
@@ -627,7 +570,7 @@ extern "C" int gs2m_tsdf_replace(gs2m_tsdf* t, const int32_t* keys, int64_t n, i
         gs2m_set_error("gs2m_tsdf_replace: block pool exhausted (%lld blocks to place, max_blocks = %u)", (long long)n, t->V.max_blocks);
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     // a reset that leaves the voxel state of the first n slots alone (they are overwritten by the unpack below, which hands out
     // exactly the slots [0, n) to n distinct in-range keys), then the unpack
     if (zero_state(t, (hipStream_t)stream, false, n)) return 1;
@@ -653,16 +596,16 @@ extern "C" int gs2m_tsdf_extract_count(gs2m_tsdf* t, gs2m_stream stream, int64_t
         gs2m_set_error("gs2m_tsdf_extract_count: NULL argument");
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     int64_t nb = 0;
     if (gs2m_tsdf_status(t, stream, &nb, nullptr, nullptr)) return 1;
     *n_triangles = 0;
     if (nb == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    gs2m_launch_mc_count(st, t->V, t->d_mc, (unsigned)nb, t->d_blk_tris, t->d_ntri);
+    gs2m_launch_mc_count(st, t->V, t->mc(), (unsigned)nb, t->d_blk_tris.get(), t->d_ntri.get());
     unsigned long long n = 0;
-    HIPCHK(hipMemcpyAsync(&n, t->d_ntri, sizeof(n), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    GS2M_HIPCHK(hipMemcpyAsync(&n, t->d_ntri.get(), sizeof(n), hipMemcpyDeviceToHost, st));
+    GS2M_HIPCHK(hipStreamSynchronize(st));
     if (n >= (1ull << 32)) {
         gs2m_set_error("mesh too large: %llu triangles (32-bit per-block offsets)", n);
         return 1;
@@ -688,68 +631,41 @@ extern "C" int gs2m_tsdf_extract_indexed(gs2m_tsdf* t, gs2m_stream stream, int64
     if (n == 0 || max_triangles == 0) return 0;
     int64_t nb = 0;
     if (gs2m_tsdf_status(t, stream, &nb, nullptr, nullptr)) return 1;
-    gs2m_launch_mc_emit((hipStream_t)stream, t->V, t->d_mc, (unsigned)nb, t->d_blk_tris, (unsigned long long)max_triangles,
+    gs2m_launch_mc_emit((hipStream_t)stream, t->V, t->mc(), (unsigned)nb, t->d_blk_tris.get(), (unsigned long long)max_triangles,
                         t->voxel_length, t->unit_length, vertices, colors, edge_index);
     return 0;
 }
 
 // ---- device-side mesh: extraction + welding, connected components ----------------------------------------------------------------
 namespace {
-// Grow-only scratch arena of the mesh passes: sub-buffers are carved out of ONE allocation that survives the call (round 5
-// hipMalloc'ed / hipFree'd ten temporaries per call: bench `cluster_ms` 69 for 0.9 ms of kernels).
-struct Arena {
-    char** p;
-    size_t* cap;
-    size_t used = 0;
-    Arena(char** p_, size_t* cap_) : p(p_), cap(cap_) {}
-    static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    bool reserve(size_t bytes) {          // total of pad(size) over the buffers about to be taken
-        used = 0;
-        if (bytes <= *cap && *p) return true;
-        (void)hipFree(*p);                // synchronises: nothing of an earlier call is in flight
-        *p = nullptr;
-        *cap = 0;
-        const size_t n = bytes + bytes / 8 + 256;
-        if (hipMalloc((void**)p, n) != hipSuccess) return false;
-        *cap = n;
-        return true;
-    }
-    template <typename T> T* take(size_t count) {
-        T* r = reinterpret_cast<T*>(*p + used);
-        used += pad(sizeof(T) * count);
-        return r;
-    }
-};
 unsigned pow2_at_least(unsigned long long n) {
     unsigned c = 1024u;
     while ((unsigned long long)c < n && c < 0x80000000u) c <<= 1;
     return c;
 }
-// gs2m_mesh_cluster has no handle: one arena per device, used under a lock (the call synchronises before it returns)
+// gs2m_mesh_cluster / gs2m_mesh_vertex_normals have no handle: one arena per device, used under that device's lock (both
+// calls synchronise before they return)
 struct DeviceScratch {
-    char* p = nullptr;
-    size_t cap = 0;
+    std::mutex lock;
+    ScratchArena arena;
 };
-DeviceScratch g_cluster_scratch[64];
-std::mutex g_cluster_lock;
+DeviceScratch& device_scratch(int device) {   // device in 0..63
+    // Process lifetime: made on first use and never deleted.  As a static object the table would be destroyed at process
+    // exit, and freeing device memory after the HIP runtime has shut down can crash or hang there.
+    static DeviceScratch* const table = new DeviceScratch[64];
+    return table[device];
+}
 }  // namespace
 
 // forget the cached mesh (its arrays stay allocated: grow-only, freed with the handle)
 static void drop_mesh(gs2m_tsdf* t) { t->mesh_nv = t->mesh_nt = 0; }
-template <typename T>
-static bool grow(T** p, size_t have, size_t need) {     // caller updates its capacity on success
-    if (need <= have && *p) return true;
-    (void)hipFree(*p);
-    *p = nullptr;
-    return hipMalloc((void**)p, sizeof(T) * (need + need / 8 + 16)) == hipSuccess;
-}
 
 extern "C" int gs2m_tsdf_extract_mesh(gs2m_tsdf* t, gs2m_stream stream, int64_t* n_vertices, int64_t* n_triangles) {
     if (!t || !n_vertices || !n_triangles) {
         gs2m_set_error("gs2m_tsdf_extract_mesh: NULL argument");
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
     drop_mesh(t);
     *n_vertices = *n_triangles = 0;
@@ -763,36 +679,25 @@ extern "C" int gs2m_tsdf_extract_mesh(gs2m_tsdf* t, gs2m_stream stream, int64_t*
     const unsigned n = (unsigned)(3 * nt);
     const unsigned cap = pow2_at_least(2ull * n);
     const unsigned m = (n + 4095u) / 4096u;
-    Arena A(&t->mesh_scratch, &t->mesh_scratch_cap);
-    const size_t need = 2 * Arena::pad(sizeof(double) * 3 * (size_t)n) + Arena::pad(sizeof(int) * 4 * (size_t)n) +
-                        Arena::pad(sizeof(unsigned long long) * (size_t)cap) + Arena::pad(sizeof(unsigned) * (size_t)cap) +
-                        3 * Arena::pad(sizeof(unsigned) * (size_t)n) + Arena::pad(sizeof(unsigned) * ((size_t)m + 2)) + Arena::pad(sizeof(int) * 4);
-    const bool tri_ok = grow(&t->mesh_tri, t->mesh_cap_t, (size_t)n);
-    if (tri_ok && (size_t)n > t->mesh_cap_t) t->mesh_cap_t = (size_t)n + (size_t)n / 8 + 16;
-    if (!tri_ok || !A.reserve(need)) {
+    double *soup_v, *soup_c;
+    int *soup_e, *small;
+    unsigned long long* hkeys;
+    unsigned *hfirst, *cell_of, *flag, *pos, *scratch;
+    if (t->mesh_tri.reserve(n) ||
+        t->mesh_scratch.carve(arena_sub(soup_v, 3 * (size_t)n), arena_sub(soup_c, 3 * (size_t)n), arena_sub(soup_e, 4 * (size_t)n),
+                              arena_sub(hkeys, cap), arena_sub(hfirst, cap), arena_sub(cell_of, n), arena_sub(flag, n),
+                              arena_sub(pos, n), arena_sub(scratch, (size_t)m + 2), arena_sub(small, 4))) {
         gs2m_set_error("gs2m_tsdf_extract_mesh: out of device memory for %lld triangles", (long long)nt);
-        if (!tri_ok) t->mesh_cap_t = 0;
-        drop_mesh(t);
         return 1;
     }
-    double* soup_v = A.take<double>(3 * (size_t)n);
-    double* soup_c = A.take<double>(3 * (size_t)n);
-    int* soup_e = A.take<int>(4 * (size_t)n);
-    unsigned long long* hkeys = A.take<unsigned long long>(cap);
-    unsigned* hfirst = A.take<unsigned>(cap);
-    unsigned* cell_of = A.take<unsigned>(n);
-    unsigned* flag = A.take<unsigned>(n);
-    unsigned* pos = A.take<unsigned>(n);
-    unsigned* scratch = A.take<unsigned>((size_t)m + 2);
-    int* small = A.take<int>(4);
     int64_t nb = 0;
     if (gs2m_tsdf_status(t, stream, &nb, nullptr, nullptr)) return 1;
-    gs2m_launch_mc_emit(st, t->V, t->d_mc, (unsigned)nb, t->d_blk_tris, (unsigned long long)nt, t->voxel_length, t->unit_length,
+    gs2m_launch_mc_emit(st, t->V, t->mc(), (unsigned)nb, t->d_blk_tris.get(), (unsigned long long)nt, t->voxel_length, t->unit_length,
                         soup_v, soup_c, soup_e);
     const int init[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0};      // mins[3], bad
-    HIPCHK(hipMemcpyAsync(small, init, sizeof(init), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(hkeys, 0xff, sizeof(unsigned long long) * (size_t)cap, st));
-    HIPCHK(hipMemsetAsync(hfirst, 0xff, sizeof(unsigned) * (size_t)cap, st));
+    GS2M_HIPCHK(hipMemcpyAsync(small, init, sizeof(init), hipMemcpyHostToDevice, st));
+    GS2M_HIPCHK(hipMemsetAsync(hkeys, 0xff, sizeof(unsigned long long) * (size_t)cap, st));
+    GS2M_HIPCHK(hipMemsetAsync(hfirst, 0xff, sizeof(unsigned) * (size_t)cap, st));
     // the compact arrays cannot be sized before the scan: first the flags, the scan and its total, then the (grow-only) arrays and the emit
     {
         int* mins = small;
@@ -800,28 +705,22 @@ extern "C" int gs2m_tsdf_extract_mesh(gs2m_tsdf* t, gs2m_stream stream, int64_t*
         gs2m_launch_mesh_weld_count(st, n, soup_e, mins, hkeys, hfirst, cap, cell_of, flag, pos, scratch, bad);
         unsigned total = 0;
         int hb[4];
-        HIPCHK(hipMemcpyAsync(&total, scratch + m, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(hb, small, sizeof(hb), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        GS2M_HIPCHK(hipMemcpyAsync(&total, scratch + m, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        GS2M_HIPCHK(hipMemcpyAsync(hb, small, sizeof(hb), hipMemcpyDeviceToHost, st));
+        GS2M_HIPCHK(hipStreamSynchronize(st));
         if (hb[3]) {
             gs2m_set_error("gs2m_tsdf_extract_mesh: the surface spans more than 2^20 voxels along an axis (62-bit weld key)");
             drop_mesh(t);
             return 1;
         }
-        const size_t nv3 = 3 * (size_t)total, nv4 = 4 * (size_t)total;
-        if (nv4 > t->mesh_cap_v) {
-            const bool ok = grow(&t->mesh_v, 0, nv3) && grow(&t->mesh_c, 0, nv3) && grow(&t->mesh_e, 0, nv4);
-            t->mesh_cap_v = ok ? nv4 : 0;
-            if (!ok) {
-                gs2m_set_error("gs2m_tsdf_extract_mesh: out of device memory for %u vertices", total);
-                drop_mesh(t);
-                return 1;
-            }
+        if (t->mesh_v.reserve(3 * (size_t)total) || t->mesh_c.reserve(3 * (size_t)total) || t->mesh_e.reserve(4 * (size_t)total)) {
+            gs2m_set_error("gs2m_tsdf_extract_mesh: out of device memory for %u vertices", total);
+            return 1;
         }
-        gs2m_launch_mesh_weld_emit(st, n, hfirst, cell_of, pos, soup_v, t->V.has_color ? soup_c : nullptr, soup_e, t->mesh_v, t->mesh_c,
-                                   t->mesh_e, t->mesh_tri);
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
+        gs2m_launch_mesh_weld_emit(st, n, hfirst, cell_of, pos, soup_v, t->V.has_color ? soup_c : nullptr, soup_e, t->mesh_v.get(), t->mesh_c.get(),
+                                   t->mesh_e.get(), t->mesh_tri.get());
+        GS2M_HIPCHK(hipStreamSynchronize(st));
+        GS2M_HIPCHK(hipGetLastError());
         t->mesh_nv = (int64_t)total;
         t->mesh_nt = nt;
     }
@@ -835,15 +734,15 @@ extern "C" int gs2m_tsdf_mesh_copy(gs2m_tsdf* t, gs2m_stream stream, double* ver
         gs2m_set_error("null handle");
         return 1;
     }
-    HIPCHK(hipSetDevice(t->device));
+    GS2M_HIPCHK(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
     if (t->mesh_nv > 0) {
-        if (vertices) HIPCHK(hipMemcpyAsync(vertices, t->mesh_v, sizeof(double) * 3 * (size_t)t->mesh_nv, hipMemcpyDefault, st));
-        if (colors) HIPCHK(hipMemcpyAsync(colors, t->mesh_c, sizeof(double) * 3 * (size_t)t->mesh_nv, hipMemcpyDefault, st));
-        if (edge_index) HIPCHK(hipMemcpyAsync(edge_index, t->mesh_e, sizeof(int) * 4 * (size_t)t->mesh_nv, hipMemcpyDefault, st));
+        if (vertices) GS2M_HIPCHK(hipMemcpyAsync(vertices, t->mesh_v.get(), sizeof(double) * 3 * (size_t)t->mesh_nv, hipMemcpyDefault, st));
+        if (colors) GS2M_HIPCHK(hipMemcpyAsync(colors, t->mesh_c.get(), sizeof(double) * 3 * (size_t)t->mesh_nv, hipMemcpyDefault, st));
+        if (edge_index) GS2M_HIPCHK(hipMemcpyAsync(edge_index, t->mesh_e.get(), sizeof(int) * 4 * (size_t)t->mesh_nv, hipMemcpyDefault, st));
     }
-    if (t->mesh_nt > 0 && triangles) HIPCHK(hipMemcpyAsync(triangles, t->mesh_tri, sizeof(int) * 3 * (size_t)t->mesh_nt, hipMemcpyDefault, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (t->mesh_nt > 0 && triangles) GS2M_HIPCHK(hipMemcpyAsync(triangles, t->mesh_tri.get(), sizeof(int) * 3 * (size_t)t->mesh_nt, hipMemcpyDefault, st));
+    GS2M_HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -855,7 +754,7 @@ extern "C" int gs2m_mesh_cluster(int device, gs2m_stream stream, int64_t n_trian
     }
     *n_clusters = 0;
     if (n_triangles == 0) return 0;
-    HIPCHK(hipSetDevice(device));
+    GS2M_HIPCHK(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     const unsigned nt = (unsigned)n_triangles;
     const unsigned cap = pow2_at_least(6ull * nt);
@@ -864,30 +763,24 @@ extern "C" int gs2m_mesh_cluster(int device, gs2m_stream stream, int64_t n_trian
         gs2m_set_error("gs2m_mesh_cluster: device %d not in 0..63", device);
         return 1;
     }
-    std::lock_guard<std::mutex> hold(g_cluster_lock);
-    Arena A(&g_cluster_scratch[device].p, &g_cluster_scratch[device].cap);
-    const size_t need = Arena::pad(sizeof(unsigned long long) * (size_t)cap) + Arena::pad(sizeof(unsigned) * (size_t)cap) +
-                        4 * Arena::pad(sizeof(unsigned) * (size_t)nt) + Arena::pad(sizeof(unsigned) * ((size_t)m + 2));
-    if (!A.reserve(need)) {
+    DeviceScratch& ds = device_scratch(device);
+    std::lock_guard<std::mutex> hold(ds.lock);
+    unsigned long long* hkeys;
+    unsigned *hval, *parent, *root, *flag, *pos, *scratch;
+    if (ds.arena.carve(arena_sub(hkeys, cap), arena_sub(hval, cap), arena_sub(parent, nt), arena_sub(root, nt), arena_sub(flag, nt),
+                       arena_sub(pos, nt), arena_sub(scratch, (size_t)m + 2))) {
         gs2m_set_error("gs2m_mesh_cluster: out of device memory for %u triangles", nt);
         return 1;
     }
-    unsigned long long* hkeys = A.take<unsigned long long>(cap);
-    unsigned* hval = A.take<unsigned>(cap);
-    unsigned* parent = A.take<unsigned>(nt);
-    unsigned* root = A.take<unsigned>(nt);
-    unsigned* flag = A.take<unsigned>(nt);
-    unsigned* pos = A.take<unsigned>(nt);
-    unsigned* scratch = A.take<unsigned>((size_t)m + 2);
-    HIPCHK(hipMemsetAsync(hkeys, 0xff, sizeof(unsigned long long) * (size_t)cap, st));
-    HIPCHK(hipMemsetAsync(hval, 0xff, sizeof(unsigned) * (size_t)cap, st));
-    HIPCHK(hipMemsetAsync(cluster_n_triangles, 0, sizeof(int64_t) * (size_t)nt, st));
+    GS2M_HIPCHK(hipMemsetAsync(hkeys, 0xff, sizeof(unsigned long long) * (size_t)cap, st));
+    GS2M_HIPCHK(hipMemsetAsync(hval, 0xff, sizeof(unsigned) * (size_t)cap, st));
+    GS2M_HIPCHK(hipMemsetAsync(cluster_n_triangles, 0, sizeof(int64_t) * (size_t)nt, st));
     gs2m_launch_mesh_cluster(st, triangles, nt, hkeys, hval, cap, parent, root, flag, pos, scratch, labels,
                              reinterpret_cast<unsigned long long*>(cluster_n_triangles));
     unsigned total = 0;
-    HIPCHK(hipMemcpyAsync(&total, scratch + m, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
+    GS2M_HIPCHK(hipMemcpyAsync(&total, scratch + m, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    GS2M_HIPCHK(hipStreamSynchronize(st));
+    GS2M_HIPCHK(hipGetLastError());
     *n_clusters = (int64_t)total;
     return 0;
 }
@@ -908,39 +801,32 @@ extern "C" int gs2m_mesh_vertex_normals(int device, gs2m_stream stream, int64_t 
         gs2m_set_error("gs2m_mesh_vertex_normals: %lld triangles and no vertices", (long long)n_triangles);
         return 1;
     }
-    HIPCHK(hipSetDevice(device));
+    GS2M_HIPCHK(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     if (n_triangles == 0) {
-        HIPCHK(hipMemsetAsync(vertex_normals, 0, sizeof(double) * 3 * (size_t)n_vertices, st));
-        HIPCHK(hipStreamSynchronize(st));
+        GS2M_HIPCHK(hipMemsetAsync(vertex_normals, 0, sizeof(double) * 3 * (size_t)n_vertices, st));
+        GS2M_HIPCHK(hipStreamSynchronize(st));
         return 0;
     }
     const unsigned nv = (unsigned)n_vertices, nt = (unsigned)n_triangles, ni = 3u * nt;
     const unsigned m = (nv + 4095u) / 4096u;
-    std::lock_guard<std::mutex> hold(g_cluster_lock);          // the per-device arena of gs2m_mesh_cluster (both calls synchronise)
-    Arena A(&g_cluster_scratch[device].p, &g_cluster_scratch[device].cap);
-    const size_t need = 3 * Arena::pad(sizeof(unsigned) * (size_t)nv) + 3 * Arena::pad(sizeof(unsigned) * (size_t)ni) +
-                        Arena::pad(sizeof(unsigned) * ((size_t)m + 2)) + Arena::pad(sizeof(unsigned) * 2);
-    if (!A.reserve(need)) {
+    DeviceScratch& ds = device_scratch(device);
+    std::lock_guard<std::mutex> hold(ds.lock);
+    unsigned *deg, *off, *fill, *list, *list2, *owner, *scratch;
+    unsigned* small;      // {bad index, largest degree}
+    if (ds.arena.carve(arena_sub(deg, nv), arena_sub(off, nv), arena_sub(fill, nv), arena_sub(list, ni), arena_sub(list2, ni),
+                       arena_sub(owner, ni), arena_sub(scratch, (size_t)m + 2), arena_sub(small, 2))) {
         gs2m_set_error("gs2m_mesh_vertex_normals: out of device memory for %u triangles", nt);
         return 1;
     }
-    unsigned* deg = A.take<unsigned>(nv);
-    unsigned* off = A.take<unsigned>(nv);
-    unsigned* fill = A.take<unsigned>(nv);
-    unsigned* list = A.take<unsigned>(ni);
-    unsigned* list2 = A.take<unsigned>(ni);
-    unsigned* owner = A.take<unsigned>(ni);
-    unsigned* scratch = A.take<unsigned>((size_t)m + 2);
-    unsigned* small = A.take<unsigned>(2);      // {bad index, largest degree}
-    HIPCHK(hipMemsetAsync(deg, 0, sizeof(unsigned) * (size_t)nv, st));
-    HIPCHK(hipMemsetAsync(fill, 0, sizeof(unsigned) * (size_t)nv, st));
-    HIPCHK(hipMemsetAsync(small, 0, sizeof(unsigned) * 2, st));
+    GS2M_HIPCHK(hipMemsetAsync(deg, 0, sizeof(unsigned) * (size_t)nv, st));
+    GS2M_HIPCHK(hipMemsetAsync(fill, 0, sizeof(unsigned) * (size_t)nv, st));
+    GS2M_HIPCHK(hipMemsetAsync(small, 0, sizeof(unsigned) * 2, st));
     gs2m_launch_mesh_normals_bucket(st, vertices, nv, triangles, nt, triangle_normals, deg, off, fill, list, owner, scratch, small);
     unsigned h_small[2] = {0u, 0u};
-    HIPCHK(hipMemcpyAsync(h_small, small, sizeof(h_small), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
+    GS2M_HIPCHK(hipMemcpyAsync(h_small, small, sizeof(h_small), hipMemcpyDeviceToHost, st));
+    GS2M_HIPCHK(hipStreamSynchronize(st));
+    GS2M_HIPCHK(hipGetLastError());
     if (h_small[0]) {
         gs2m_set_error("gs2m_mesh_vertex_normals: a triangle names a vertex outside 0..%u", nv - 1);
         return 1;
@@ -953,7 +839,7 @@ extern "C" int gs2m_mesh_vertex_normals(int device, gs2m_stream stream, int64_t 
         if (width > 0x7fffffffu) break;
     }
     gs2m_launch_mesh_vertex_sum(st, nv, nt, off, deg, list, triangle_normals, vertex_normals);
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
+    GS2M_HIPCHK(hipStreamSynchronize(st));
+    GS2M_HIPCHK(hipGetLastError());
     return 0;
 }

@@ -37,8 +37,8 @@ extern "C" const char* gs2m_last_error(void) { return g_err; }
 def build_png_emu():
     """tests/emu/_build/libgs2mesh_png_emu.so: png_encode.hip + the fiber emulator (rebuilt when a source is newer)."""
     os.makedirs(OUT, exist_ok=True)
-    deps = [SRC, os.path.join(EMU, "platform.h"), os.path.join(EMU, "emu_runtime.cpp"), os.path.abspath(__file__),
-            os.path.join(ROOT, "include", "gs2mesh_amd.h")]
+    deps = [SRC, os.path.join(os.path.dirname(SRC), "device_memory.h"), os.path.join(EMU, "platform.h"),
+            os.path.join(EMU, "emu_runtime.cpp"), os.path.abspath(__file__), os.path.join(ROOT, "include", "gs2mesh_amd.h")]
     if os.path.exists(LIB) and os.path.getmtime(LIB) >= max(os.path.getmtime(d) for d in deps):
         return LIB
     err = os.path.join(OUT, "png_emu_errors.cpp")
