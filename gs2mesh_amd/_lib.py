@@ -85,6 +85,9 @@ _PROTOS = {
     "gs2m_stereo_sgm": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp]),
     "gs2m_knn_scratch_bytes": (i64, [i32]),
     "gs2m_knn_mean_dist2": (i32, [i32, vp, vp, vp, i64, vp, vp]),
+    "gs2m_photo_loss_scratch_bytes": (i64, [i32, i32, i32]),
+    "gs2m_photo_loss_forward": (i32, [i32, i32, i32, vp, vp, f32, vp, i64, vp, vp, vp, vp]),
+    "gs2m_photo_loss_backward": (i32, [i32, i32, i32, vp, vp, vp, f32, vp, vp, vp]),
     "gs2m_mask_preprocess": (i32, [i32, i32, i32, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, C.POINTER(vp), vp, vp]),
     "gs2m_tsdf_create": (i32, [C.POINTER(vp), f64, f64, i32, i32, i32, i64, i32]),
     "gs2m_tsdf_destroy": (i32, [vp]),

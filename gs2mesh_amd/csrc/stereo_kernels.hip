@@ -21,6 +21,7 @@
 #include "mask_kernels.h"
 #include "sgm_kernels.h"
 #include "knn_kernels.h"
+#include "loss_kernels.h"
 
 void gs2m_set_error(const char* fmt, ...);
 
@@ -166,5 +167,65 @@ extern "C" int gs2m_knn_mean_dist2(int P, const float* points, const int32_t* or
         return 1;
     }
     knn_launch((hipStream_t)stream, P, points, order, knn_scratch_layout(scratch, P), out);
+    return 0;
+}
+
+// 0: nothing to do, 1: refused (the message is set), 2: go
+static int loss_check_sizes(const char* fn, int planes, int height, int width) {
+    if (planes < 0 || height < 0 || width < 0) {
+        gs2m_set_error("%s: negative %s (%d x %d x %d)", fn, planes < 0 ? "planes" : height < 0 ? "height" : "width", planes, height,
+                       width);
+        return 1;
+    }
+    if (planes == 0 || height == 0 || width == 0) return 0;
+    if (const int64_t tiles = loss_tiling(planes, height, width).tiles; tiles <= 0 || tiles > LOSS_MAX_TILES) {
+        gs2m_set_error("%s: size %d x %d x %d is more than %d tiles of %d x %d", fn, planes, height, width, LOSS_MAX_TILES,
+                       LOSS_TW, LOSS_TH);
+        return 1;
+    }
+    return 2;
+}
+
+extern "C" int64_t gs2m_photo_loss_scratch_bytes(int planes, int height, int width) {
+    if (planes <= 0 || height <= 0 || width <= 0) return 0;
+    const int64_t tiles = loss_tiling(planes, height, width).tiles;
+    return tiles <= 0 || tiles > LOSS_MAX_TILES ? -1 : 16 * ((tiles + 1) / 2);                        // a pair of floats per tile
+}
+
+extern "C" int gs2m_photo_loss_forward(int planes, int height, int width, const float* image, const float* target,
+                                       float lambda_dssim, void* scratch, int64_t scratch_bytes, float* out, float* partials,
+                                       float* tap_map, gs2m_stream stream) {
+    const int go = loss_check_sizes("gs2m_photo_loss_forward", planes, height, width);
+    if (go != 2) return go;
+    if (!image || !target || !out) {
+        gs2m_set_error("gs2m_photo_loss_forward: NULL %s", !image ? "image" : !target ? "target" : "out");
+        return 1;
+    }
+    const int64_t need = gs2m_photo_loss_scratch_bytes(planes, height, width);
+    if (!scratch || scratch_bytes < need) {
+        gs2m_set_error("gs2m_photo_loss_forward: scratch of %lld bytes, gs2m_photo_loss_scratch_bytes asks for %lld",
+                       (long long)(scratch ? scratch_bytes : 0), (long long)need);
+        return 1;
+    }
+    if ((uintptr_t)scratch & 15u) {
+        gs2m_set_error("gs2m_photo_loss_forward: scratch must be 16-byte aligned");
+        return 1;
+    }
+    loss_launch_forward((hipStream_t)stream, planes, height, width, image, target, lambda_dssim, (float*)scratch, out, partials,
+                        tap_map);
+    return 0;
+}
+
+extern "C" int gs2m_photo_loss_backward(int planes, int height, int width, const float* image, const float* target,
+                                        const float* partials, float lambda_dssim, const float* grad_loss, float* grad_image,
+                                        gs2m_stream stream) {
+    const int go = loss_check_sizes("gs2m_photo_loss_backward", planes, height, width);
+    if (go != 2) return go;
+    if (!image || !target || !partials || !grad_loss || !grad_image) {
+        gs2m_set_error("gs2m_photo_loss_backward: NULL %s", !image ? "image" : !target ? "target" : !partials ? "partials"
+                                                                 : !grad_loss ? "grad_loss" : "grad_image");
+        return 1;
+    }
+    loss_launch_backward((hipStream_t)stream, planes, height, width, image, target, partials, lambda_dssim, grad_loss, grad_image);
     return 0;
 }

@@ -88,7 +88,130 @@ def loss_fn(image, gt, lambda_dssim):
     return (1.0 - lambda_dssim) * l1_loss(image, gt) + lambda_dssim * (1.0 - ssim(image, gt))
 
 
-def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False, seed=0, callback=None, timing=None):
+# ---- the fused loss: gs2m_photo_loss_forward / _backward (gs2mesh_amd/csrc/loss_kernels.h) -----------------------------------
+_LOSS_SCRATCH = {}      # device -> grow-only scratch buffer
+
+
+def _loss_scratch(like, nbytes):
+    from .rasterizer import _empty, _is_torch
+    key = str(like.device) if _is_torch(like) else "numpy"
+    buf = _LOSS_SCRATCH.get(key)
+    if buf is None or buf.shape[0] * 8 < nbytes:
+        buf = _LOSS_SCRATCH[key] = _empty(like, ((nbytes + 15) // 16 * 2,), np.int64)
+    return buf
+
+
+def _loss_planes(image, gt, what):
+    from .rasterizer import _is_torch
+    if tuple(image.shape) != tuple(gt.shape) or image.ndim not in (3, 4):
+        raise ValueError(f"{what}: image and target must be [C,H,W] or [B,C,H,W] of one shape, got {tuple(image.shape)} and "
+                         f"{tuple(gt.shape)}")
+    f32 = torch.float32 if _is_torch(image) else np.float32
+    if image.dtype != f32 or gt.dtype != f32:
+        raise TypeError(f"{what}: image and target must be float32, got {image.dtype} and {gt.dtype}")
+    H, W = int(image.shape[-2]), int(image.shape[-1])
+    return int(np.prod(image.shape[:-2], dtype=np.int64)), H, W
+
+
+def photo_loss_forward(image, gt, lambda_dssim, want_partials=True, want_map=False, lib=None, stream=None):
+    """``gs2m_photo_loss_forward`` on contiguous f32 device tensors (numpy arrays on the emulator back-end of the tests).
+    -> (out [3] = loss, mean |x - y|, mean SSIM; partials [3,*image.shape] or None; the SSIM map or None).  Asynchronous on
+    the stream; the scratch is kept per device (shared by every stream of it: order the calls on one) and only grows."""
+    from . import _lib
+    from .rasterizer import _empty, _ptr, _stream_of
+    lib = lib or _lib.get()
+    planes, H, W = _loss_planes(image, gt, "photo_loss_forward")
+    if planes * H * W == 0:
+        raise ValueError("photo_loss_forward: empty image")
+    need = int(lib.gs2m_photo_loss_scratch_bytes(planes, H, W))
+    if need < 0:
+        raise ValueError(f"photo_loss_forward: unsupported size {tuple(image.shape)}")
+    scratch = _loss_scratch(image, need)
+    out = _empty(image, (3,), np.float32)
+    partials = _empty(image, (3,) + tuple(image.shape), np.float32) if want_partials else None
+    tap = _empty(image, tuple(image.shape), np.float32) if want_map else None
+    _lib.check(lib.gs2m_photo_loss_forward(planes, H, W, _ptr(image, None, "image"), _ptr(gt, None, "target"), float(lambda_dssim),
+                                           _ptr(scratch), scratch.shape[0] * 8, _ptr(out), _ptr(partials), _ptr(tap),
+                                           _stream_of(image, stream)), lib)
+    return out, partials, tap
+
+
+def photo_loss_backward(image, gt, partials, lambda_dssim, grad_loss, lib=None, stream=None):
+    """``gs2m_photo_loss_backward``: ``grad_loss`` is a one-element f32 buffer on the device (never read on the host).
+    -> dL/d image, of ``image``'s shape."""
+    from . import _lib
+    from .rasterizer import _empty, _ptr, _stream_of
+    lib = lib or _lib.get()
+    planes, H, W = _loss_planes(image, gt, "photo_loss_backward")
+    if tuple(partials.shape) != (3,) + tuple(image.shape):
+        raise ValueError(f"photo_loss_backward: partials must be {(3,) + tuple(image.shape)}, got {tuple(partials.shape)}")
+    if int(np.prod(grad_loss.shape, dtype=np.int64)) != 1:
+        raise ValueError(f"photo_loss_backward: grad_loss must hold one element, got {tuple(grad_loss.shape)}")
+    grad = _empty(image, tuple(image.shape), np.float32)
+    _lib.check(lib.gs2m_photo_loss_backward(planes, H, W, _ptr(image, None, "image"), _ptr(gt, None, "target"),
+                                            _ptr(partials, None, "partials"), float(lambda_dssim),
+                                            _ptr(grad_loss, None, "grad_loss"), _ptr(grad), _stream_of(image, stream)), lib)
+    return grad
+
+
+class _FusedLoss(torch.autograd.Function):
+    """out[which] of the forward kernel; the backward kernel with autograd's incoming gradient as its device scalar"""
+
+    @staticmethod
+    def forward(ctx, image, gt, lambda_dssim, which, need_grad, lib):
+        out, partials, _ = photo_loss_forward(image, gt, lambda_dssim, want_partials=need_grad, lib=lib)
+        if need_grad:
+            ctx.save_for_backward(image, gt, partials)
+        ctx.args = (lambda_dssim, which, lib)
+        return out[which]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        image, gt, partials = ctx.saved_tensors
+        lambda_dssim, which, lib = ctx.args
+        g = grad_output.to(torch.float32).reshape(1).contiguous()
+        if which == 2:                      # mean SSIM = 1 - loss at lambda = 1
+            g = -g
+        return photo_loss_backward(image, gt, partials, lambda_dssim, g, lib=lib), None, None, None, None, None
+
+
+def _fused(image, gt, lambda_dssim, which, lib, what):
+    from .rasterizer import _is_torch
+    if not _is_torch(image):                # the emulator back-end of the tests: the value alone, no graph
+        return photo_loss_forward(np.ascontiguousarray(image), np.ascontiguousarray(gt), lambda_dssim, want_partials=False,
+                                  lib=lib)[0][which]
+    if not _is_torch(gt):
+        raise TypeError(f"{what}: the target must be a torch tensor like the image")
+    if gt.requires_grad:
+        raise RuntimeError(f"{what}: no gradient is computed for the target; detach it")
+    _loss_planes(image, gt, what)
+    from . import _lib
+    image = image.contiguous()              # the one copy of a non-contiguous render; autograd carries the gradient back
+    _lib.MEMORY.ptr(image.detach(), torch.float32, "image")                 # a CPU tensor is an error, before any work
+    need_grad = torch.is_grad_enabled() and image.requires_grad
+    return _FusedLoss.apply(image, gt.contiguous(), float(lambda_dssim), which, need_grad, lib)
+
+
+def fused_loss(image, gt, lambda_dssim, *, lib=None):
+    """``loss_fn`` on the HIP kernels of ``gs2m_photo_loss_forward`` / ``_backward`` (include/gs2mesh_amd.h states the
+    arithmetic and how far it is from ``loss_fn``): a 0-d tensor, differentiable in ``image``.  ``image``, ``gt``: f32 on the HIP
+    device, [3,H,W], [C,H,W] or [B,C,H,W] (the leading dimensions are planes).  Window 11 only; a ``gt`` that requires grad
+    raises.  The partial derivatives are written only when ``image`` requires grad.  There is no double backward.  The
+    scratch of the tile sums is one buffer per device: calls on one device must be ordered on one stream (two streams
+    calling concurrently would race on it, as with ``simple_knn``'s scratch)."""
+    return _fused(image, gt, lambda_dssim, 0, lib, "fused_loss")
+
+
+def fused_ssim(img1, img2, *, lib=None):
+    """The mean of ``ssim(img1, img2)`` through the same kernels, differentiable in ``img1``: the drop-in for code that
+    calls ``ssim(a, b)`` on its own.  It takes the two images only (window 11, the mean): a third positional argument, as in
+    ``ssim(a, b, 11)``, is a TypeError.  One scratch buffer per device, as ``fused_loss``."""
+    return _fused(img1, img2, 1.0, 2, lib, "fused_ssim")
+
+
+def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False, seed=0, callback=None, timing=None,
+          loss="torch"):
     """The loop of train.py:51-128 over ``opt.iterations`` iterations -> the loss of every iteration.
 
     ``gaussians``: a ``GaussianModel`` after ``training_setup(opt)``; ``cameras``: ``graphics.Camera`` objects; ``images``: the
@@ -96,8 +219,12 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
     the device.  ``seed`` drives the choice of views (a stack refilled when empty, popped at random) and the random
     background.  ``callback(iteration, event, gaussians, counts)`` is called after every densification (``"densify"``, with the
     ``{"cloned", "split", "pruned"}`` counts of ``densify_and_prune``) and opacity reset (``"reset_opacity"``, None).  ``timing``: None, or a dict that receives the stream time in ms of the four phases of
-    every iteration (lists under ``render``, ``loss``, ``backward``, ``update``), measured with events and read at the end."""
+    every iteration (lists under ``render``, ``loss``, ``backward``, ``update``), measured with events and read at the end.
+    ``loss``: ``"torch"`` (``loss_fn``, the default) or ``"fused"`` (``fused_loss``, the HIP kernels)."""
+    if loss not in ("torch", "fused"):
+        raise ValueError(f"train: loss must be 'torch' or 'fused', got {loss!r}")
     from .gaussian_renderer import render
+    loss_of = fused_loss if loss == "fused" else loss_fn
     rng = random.Random(seed)
     pipe = PipelineParams()
     losses = []
@@ -124,7 +251,7 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
         image, viewspace, visible, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
         if t:
             t.append(mark())
-        loss = loss_fn(image, images[view], opt.lambda_dssim)
+        loss = loss_of(image, images[view], opt.lambda_dssim)
         if t:
             t.append(mark())
         loss.backward()

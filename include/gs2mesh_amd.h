@@ -36,8 +36,8 @@ extern "C" {
                             gs2m_mesh_cluster, gs2m_raster_blend_cycles, GS2M_OPT_BLEND_MODE / _PROFILE) + round 6
                             (gs2m_tsdf_flags_device, GS2M_OPT_BIN_LANE_TILES, GS2M_OPT_PROJECT_SHARED_READ, GS2M_OPT_EXACT_TILE_CULL level 2; GS2M_OPT_BLEND_MODE 1
                             removed).  Added since without a new number: gs2m_stereo_sgm / gs2m_stereo_sgm_scratch_bytes,
-                            gs2m_knn_mean_dist2 / gs2m_knn_scratch_bytes.  The Python binding checks it at
-                            load time */
+                            gs2m_knn_mean_dist2 / gs2m_knn_scratch_bytes, gs2m_photo_loss_forward / _backward /
+                            _scratch_bytes.  The Python binding checks it at load time */
 
 typedef void* gs2m_stream; /* hipStream_t */
 
@@ -639,6 +639,56 @@ int gs2m_stereo_sgm(const uint8_t* left_rgb8, const uint8_t* right_rgb8, int wid
 int64_t gs2m_knn_scratch_bytes(int P);
 int gs2m_knn_mean_dist2(int P, const float* points, const int32_t* order, void* scratch, int64_t scratch_bytes, float* out,
                         gs2m_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* photometric loss of 3DGS training (L1 + D-SSIM, GS/utils/loss_utils.py, train.py:89-90) */
+/* ------------------------------------------------------------------------------------ */
+
+/*
+ * loss = (1 - lambda) * mean|x - y| + lambda * (1 - mean(m)),  m the SSIM map of x = image and y = target: 11 x 11 Gaussian
+ * window (sigma 1.5, normalised), zero padding, per plane, C1 = 0.01^2, C2 = 0.03^2.  N = planes * height * width.
+ * Defined operation by operation in f32, every operation rounded on its own (no FMA, IEEE division), parentheses = order:
+ *   - w[k], k = 0 .. 10: exp(-(k - 5)^2 / 4.5) normalised by the sum in index order, in double on the host, cast to f32 last;
+ *   - F(q) = V(H(q)), H(q)(r, c) = sum_k w[k] * q(r, c + k - 5), V(h)(r, c) = sum_k w[k] * h(r + k - 5, c); every sum is
+ *     acc = 0, then acc = acc + w[k] * term for k = 0 .. 10; q and H(q) are 0 outside the image (the 2-D window is the outer
+ *     product of w, so this is the reference's filter at 22 taps);
+ *   - mu1 = F(x), mu2 = F(y), exx = F(x * x), eyy = F(y * y), exy = F(x * y);  m11 = mu1 * mu1, m22 = mu2 * mu2,
+ *     m12 = mu1 * mu2, s1 = exx - m11, s2 = eyy - m22, s12 = exy - m12;
+ *   - A = (m11 + m22) + C1, B = (s1 + s2) + C2, C = 2 * m12 + C1, D = 2 * s12 + C2, AB = A * B, m = (C * D) / AB
+ *     (identical images give m = 1 exactly);
+ *   - partials[0] = dm/dmu1 = 2 * ((((mu2 * D) / AB - (mu2 * C) / AB) - (mu1 * m) / A) + (mu1 * m) / B),
+ *     partials[1] = dm/dsigma1^2 = -(m / B),  partials[2] = dm/dsigma12 = (2 * C) / AB;
+ *   - out = { (ka * S1 + f32(lambda)) - kb * Sm,  S1 * f32(1 / N),  Sm * f32(1 / N) } with S1 = sum |x - y|, Sm = sum m,
+ *     ka = f32((1 - lambda) / N), kb = f32(lambda / N), the quotients in double.  The sums use no atomics and a fixed order
+ *     (per thread, a tree per 32 x 16 tile, then one workgroup over the tiles): the same bits on every run, and the longest
+ *     addition chain is 2 + 8 + ceil(tiles / 1024) + 10, tiles = planes * ceil(height / 16) * ceil(width / 32);
+ *   - backward: gl = grad_loss[0], g = gl * (-kb), l = gl * ka,
+ *     grad_image = ((F(g * partials[0]) + (2 * x) * F(g * partials[1])) + y * F(g * partials[2])) + l * sign(x - y),
+ *     sign = (d > 0) - (d < 0), so 0 where x = y as torch's abs has it.  No gradient is computed for the target.
+ * Measured against the fp64 evaluation of the reference's formulas on the four inputs of tests/test_photo_loss_statement.py
+ * (N from 84 to 23 040; the f32 torch path on the same inputs in brackets): SSIM map 1.9e-6 on noise [5.1e-6], up to 3.7e-4
+ * on smooth near-identical images, where sigma^2 cancels [9.2e-4]; loss at most 8.4e-7 [2.7e-7]; the gradient scales with
+ * 1 / N, and N * |error| is at most 2.4e-4 [5.8e-4] (entries N * |g| up to 8.4).  Stated tolerance against fp64: loss 1e-6 plus
+ * 2^-24 per addition of the chain, map 4e-4, gradient 3e-4 / N.  Stated tolerance against loss_fn evaluated in f32, which errs
+ * too (the two measured errors added; for the loss also the chain's 21 * 2^-24): loss 2.5e-6, gradient 1e-3 / N.
+ *   planes, height, width   planes * height * width = 0 does nothing and returns 0; at most 2^23 tiles
+ *   image, target           [planes][height][width] f32 device
+ *   lambda_dssim            the reference's 0.2
+ *   scratch, scratch_bytes  device, 16-byte aligned, at least gs2m_photo_loss_scratch_bytes (-1 for sizes it refuses);
+ *                           nothing in it outlives the call
+ *   out                     [3] f32 device: loss, mean |x - y|, mean SSIM
+ *   partials                NULL (no backward will follow), or [3][planes][height][width] f32 device
+ *   tap_map                 NULL, or [planes][height][width] f32 device: m (tests)
+ *   grad_loss               [1] f32 device: autograd's incoming gradient, never read on the host
+ *   grad_image              [planes][height][width] f32 device, written in full
+ * Stateless, asynchronous on `stream`, no allocation; a NULL pointer, a negative size and a short or misaligned scratch
+ * return 1 with a gs2m_last_error() that names the argument.
+ */
+int64_t gs2m_photo_loss_scratch_bytes(int planes, int height, int width);
+int gs2m_photo_loss_forward(int planes, int height, int width, const float* image, const float* target, float lambda_dssim,
+                            void* scratch, int64_t scratch_bytes, float* out, float* partials, float* tap_map, gs2m_stream stream);
+int gs2m_photo_loss_backward(int planes, int height, int width, const float* image, const float* target, const float* partials,
+                             float lambda_dssim, const float* grad_loss, float* grad_image, gs2m_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* PNG encoder (the Renderer's left.png / right.png)               */

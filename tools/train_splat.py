@@ -1,12 +1,13 @@
 """Train a Gaussian splat on one GPU: point cloud + posed images -> point_cloud/iteration_N/point_cloud.ply.
 
-    python tools/train_splat.py <colmap_dir> <out_dir> [--iterations N] [--resolution-scale s]
-    python tools/train_splat.py --synthetic <out_dir> [--iterations N]
+    python tools/train_splat.py <colmap_dir> <out_dir> [--iterations N] [--resolution-scale s] [--loss {torch,fused}]
+    python tools/train_splat.py --synthetic <out_dir> [--iterations N] [--loss {torch,fused}]
 
 <colmap_dir> holds a COLMAP text model (sparse/0/cameras.txt, images.txt, points3D.txt; PINHOLE or SIMPLE_PINHOLE cameras)
 and images/.  <out_dir>/point_cloud/iteration_N/point_cloud.ply is where `Renderer` and `GaussianModel.load_ply` look.
 --synthetic trains against renders of `synthetic.textured_sphere` instead (no dataset needed).  Prints the wall time per
 iteration and its split into render forward, loss, backward and optimiser + densification (stream time between events).
+--loss fused computes L1 + D-SSIM and its gradient with the HIP kernels (training.fused_loss) instead of torch ops.
 """
 import argparse
 import json
@@ -63,6 +64,7 @@ def main():
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--white-background", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--loss", choices=("torch", "fused"), default="torch", help="torch ops (default) or the fused HIP kernels")
     ap.add_argument("--synthetic-size", type=int, nargs=4, default=[20000, 4000, 800, 600], metavar=("P_TRUE", "P_INIT", "W", "H"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -99,7 +101,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     losses = training.train(g, cameras, images, opt, extent=extent, bg=bg, white_background=a.white_background, seed=a.seed,
-                            timing=timing)
+                            timing=timing, loss=a.loss)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     ply_dir = os.path.join(out_dir, "point_cloud", f"iteration_{a.iterations}")
@@ -113,7 +115,7 @@ def main():
     split = {name: statistics.fmean(v) for name, v in timing.items()}
     print(json.dumps({
         "ply": ply, "views": len(cameras), "width": cameras[0].image_width, "height": cameras[0].image_height,
-        "iterations": a.iterations, "gaussians_start": P0, "gaussians_end": int(g.get_xyz.shape[0]),
+        "iterations": a.iterations, "loss_path": a.loss, "gaussians_start": P0, "gaussians_end": int(g.get_xyz.shape[0]),
         "loss_first_tenth": statistics.fmean(losses[:k]), "loss_last_tenth": statistics.fmean(losses[-k:]),
         "wall_ms_per_iteration": 1e3 * wall / max(1, a.iterations),
         "stream_ms_per_iteration": {"render_forward": split["render"], "loss": split["loss"], "backward": split["backward"],
