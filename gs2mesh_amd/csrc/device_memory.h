@@ -6,6 +6,7 @@
 //   PinnedBuffer   one hipHostMalloc allocation
 //   ScratchArena   one DeviceBuffer carved into the temporaries of a call
 //   EventPool      the recycled event pairs of the stage timers
+//   StageTimer     one timed stage launch: a rocTX range and, when timing is on, an event pair of the pool around it
 //
 // Two rules.  Growth frees with the SYNCHRONISING hipFree before it allocates, so nothing in flight can still be using the
 // old memory and no call site has to think about it (contents are not kept).  And none of these types may be a static
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "platform.h"
+#include "roctx_ranges.h"
 
 void gs2m_set_error(const char* fmt, ...);
 
@@ -153,6 +155,9 @@ public:
         hipEvent_t e;
         return hipEventCreate(&e) == hipSuccess ? e : nullptr;
     }
+    void put(hipEvent_t e) {   // an event of get() that was never pushed goes back
+        if (e) free_.push_back(e);
+    }
     // a and b were recorded around a launch of `stage`; it counts as `weight` launches (a batch: its frames)
     void push(int stage, hipEvent_t a, hipEvent_t b, int weight = 1) { live_.push_back({stage, a, b, weight}); }
     // adds what was pushed since the last drain to total_ms[n_stages] / launches[n_stages]; the stream must be idle
@@ -167,5 +172,39 @@ public:
             free_.push_back(p.b);
         }
         live_.clear();
+    }
+};
+
+// RAII around one stage launch: a rocTX range `name` (GS2M_ROCTX=1) and, when `enabled`, an event pair recorded on `st` and
+// pushed to the pool as `weight` launches of `stage`.  Without events to be had the launch goes untimed.
+class StageTimer {
+    EventPool& pool_;
+    hipStream_t st_;
+    hipEvent_t a_ = nullptr, b_ = nullptr;
+    int stage_, weight_;
+    Gs2mRange range_;
+
+public:
+    StageTimer(EventPool& pool, bool enabled, hipStream_t st, int stage, const char* name, int weight = 1)
+        : pool_(pool), st_(st), stage_(stage), weight_(weight), range_(name) {
+        if (enabled) {
+            a_ = pool_.get();
+            b_ = pool_.get();
+            if (a_ && b_) {
+                (void)hipEventRecord(a_, st_);
+            } else {   // half a pair times nothing
+                pool_.put(a_);
+                pool_.put(b_);
+                a_ = b_ = nullptr;
+            }
+        }
+    }
+    StageTimer(const StageTimer&) = delete;
+    StageTimer& operator=(const StageTimer&) = delete;
+    ~StageTimer() {
+        if (a_) {
+            (void)hipEventRecord(b_, st_);
+            pool_.push(stage_, a_, b_, weight_);
+        }
     }
 };

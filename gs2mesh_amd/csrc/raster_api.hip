@@ -11,7 +11,6 @@
 #include "../../include/gs2mesh_amd.h"
 #include "device_memory.h"
 #include "raster_internal.h"
-#include "roctx_ranges.h"
 
 // ---- error plumbing ---------------------------------------------------------------------------
 static thread_local std::string g_err;
@@ -250,26 +249,10 @@ static int dbg_check(gs2m_raster* r, hipStream_t st, const char* what) {
 
 static const char* const kStageRange[GS2M_N_STAGES] = {"gs2m:project", "gs2m:hist_colscan", "gs2m:tile_scan", "gs2m:scatter",
                                                         "gs2m:sort_tiles", "gs2m:blend", "gs2m:count_tiles"};
-struct StageTimer {  // RAII: a rocTX range (GS2M_ROCTX=1) and, when timing is on, an event pair around one stage launch
-    gs2m_raster* r;
-    hipStream_t st;
-    hipEvent_t a = nullptr, b = nullptr;
-    int stage;
-    Gs2mRange range;
-    StageTimer(gs2m_raster* r_, hipStream_t st_, int stage_) : r(r_), st(st_), stage(stage_), range(kStageRange[stage_]) {
-        if (r->opt_timing) {
-            a = r->events.get();
-            b = r->events.get();
-            if (a) (void)hipEventRecord(a, st);
-        }
-    }
-    ~StageTimer() {
-        if (a && b) {
-            (void)hipEventRecord(b, st);
-            r->events.push(stage, a, b);
-        }
-    }
-};
+// one timed stage of a pass: its rocTX range and, with GS2M_OPT_STAGE_TIMING, its event pair
+static StageTimer stage_timer(gs2m_raster* r, hipStream_t st, int stage) {
+    return StageTimer(r->events, r->opt_timing != 0, st, stage, kStageRange[stage]);
+}
 
 // One fused pass over `pairs` groups of nv (<= GS2M_MAX_VIEWS) views whose CamUniforms are already in r->d_cams (host_cams ==
 // null) or travel with the projection launch (host_cams = the nv * pairs host-side uniforms).
@@ -337,42 +320,42 @@ static int run_views(gs2m_raster* r, const GaussIn& g, int nv, int pairs, int W,
     // going on from registers -- measured 51 vs 28 + 28 us on C2 and 212 vs 135 + 80 us on C3: the counting step is bound by
     // its own LDS atomics and tile tests, not by re-reading the records; 128 VGPRs for 1024-thread workgroups.  Not kept.)
     {
-        StageTimer tm(r, st, GS2M_STAGE_PROJECT);
+        StageTimer tm = stage_timer(r, st, GS2M_STAGE_PROJECT);
         gs2m_launch_project(nv, pairs, st, g, r->d_cams.get(), recs, out_radii, cull_arg_p, host_cams, r->opt_project_shared);
     }
     if (dbg_check(r, st, "project")) return 1;
     {
-        StageTimer tm(r, st, GS2M_STAGE_COUNT);
+        StageTimer tm = stage_timer(r, st, GS2M_STAGE_COUNT);
         if (gs2m_launch_count_tiles(nv, pairs, n_wg, wg_threads, lds_p, st, recs, g.P, r->d_cams.get(), chunk, r->d_hist.get(), r->d_tilemask.get(),
                                     cull_arg_p, g.ids != nullptr, r->opt_bin_lane_tiles))
             return 1;
     }
     if (dbg_check(r, st, "count_tiles")) return 1;
     {
-        StageTimer tm(r, st, GS2M_STAGE_COLSCAN);
+        StageTimer tm = stage_timer(r, st, GS2M_STAGE_COLSCAN);
         gs2m_launch_hist_colscan(st, nvt, r->d_hist.get(), n_wg, tiles, r->d_tile_count.get());
     }
     if (dbg_check(r, st, "hist_colscan")) return 1;
     {
-        StageTimer tm(r, st, GS2M_STAGE_TILESCAN);
+        StageTimer tm = stage_timer(r, st, GS2M_STAGE_TILESCAN);
         gs2m_launch_tile_scan(st, nvt, r->d_tile_count.get(), r->d_tile_start.get(), tiles, gx, r->h_status.get() + 1 + status_slot, r->d_status.get(), cap, r->d_sort_lists.get());
     }
     if (dbg_check(r, st, "tile_scan")) return 1;
     {
-        StageTimer tm(r, st, GS2M_STAGE_SCATTER);
+        StageTimer tm = stage_timer(r, st, GS2M_STAGE_SCATTER);
         if (gs2m_launch_scatter(nv, pairs, n_wg, wg_threads, lds, st, recs, g.P, r->d_cams.get(), chunk, r->d_hist.get(), r->d_tile_start.get(),
                                 r->d_tilemask.get(), r->d_keys.get(), cap, cull_arg_s, g.ids, g.ids != nullptr, r->opt_bin_lane_tiles))
             return 1;
     }
     if (dbg_check(r, st, "scatter")) return 1;
     {
-        StageTimer tm(r, st, GS2M_STAGE_SORT);
+        StageTimer tm = stage_timer(r, st, GS2M_STAGE_SORT);
         // class-grid hint: snapshotted at the top of the pass
         gs2m_launch_sort_tiles(st, nvt, r->d_keys.get(), r->d_tmp.get(), r->d_tile_start.get(), tiles, cap, r->d_sort_lists.get(), hint);
     }
     if (dbg_check(r, st, "sort_tiles")) return 1;
     {
-        StageTimer tm(r, st, GS2M_STAGE_BLEND);
+        StageTimer tm = stage_timer(r, st, GS2M_STAGE_BLEND);
         if (gs2m_launch_blend(st, r->opt_blend, r->opt_tile_rows, nvt, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, r->d_cams.get(),
                               g.P, cap, out_color, out_rgb8, g.ids ? r->run_rank : nullptr,
                               r->d_sort_lists.get() + (size_t)nvt * GS2M_SORT_CLASSES_API * (tiles + 1), r->opt_blend_mode,

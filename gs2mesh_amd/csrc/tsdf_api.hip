@@ -11,7 +11,6 @@
 #include "device_memory.h"
 #include "tsdf_common.h"
 #include "tsdf_internal.h"
-#include "roctx_ranges.h"
 
 struct gs2m_tsdf {
     int device = 0;
@@ -244,6 +243,18 @@ static int fill_frame(gs2m_tsdf* t, TsdfFrame& f, int width, int height, double 
     return 0;
 }
 
+// size and intrinsics as both integrate entry points require them; `max_side`: the largest width / height the caller's kernels
+// can address (0 = no limit of their own), named by `limit_note`
+static int check_frame_geometry(const char* who, int width, int height, double fx, double fy, double depth_scale, int max_side,
+                                const char* limit_note) {
+    if (width <= 0 || height <= 0 || (max_side && (width > max_side || height > max_side)) || !(fx != 0) || !(fy != 0) ||
+        !(depth_scale != 0)) {
+        gs2m_set_error("%s: bad intrinsics / size%s", who, limit_note);
+        return 1;
+    }
+    return 0;
+}
+
 extern "C" int gs2m_tsdf_integrate(gs2m_tsdf* t, const float* depth, const uint8_t* color, const uint8_t* mask,
                                    int width, int height, double fx, double fy, double cx, double cy,
                                    const double* extrinsic_w2c, double depth_scale, double depth_trunc,
@@ -257,42 +268,21 @@ extern "C" int gs2m_tsdf_integrate(gs2m_tsdf* t, const float* depth, const uint8
         gs2m_set_error("[ScalableTSDFVolume::Integrate] Unsupported image format.");
         return 1;
     }
-    if (width <= 0 || height <= 0 || !(fx != 0) || !(fy != 0) || !(depth_scale != 0)) {
-        gs2m_set_error("gs2m_tsdf_integrate: bad intrinsics / size");
-        return 1;
-    }
+    if (check_frame_geometry("gs2m_tsdf_integrate", width, height, fx, fy, depth_scale, 0, "")) return 1;
     GS2M_HIPCHK(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
     TsdfFrame f;
     if (fill_frame(t, f, width, height, fx, fy, cx, cy, extrinsic_w2c, depth_scale, depth_trunc, min_depth, mask != nullptr))
         return 1;
     GS2M_HIPCHK(hipMemsetAsync(t->V.counters + 1, 0, sizeof(unsigned), st));  // touched_count = 0
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    if (t->timing) {
-        e0 = t->events.get();
-        e1 = t->events.get();
-        e2 = t->events.get();
-        e3 = t->events.get();
-    }
-    const bool tm = e0 && e1 && e2 && e3;
-    if (tm) (void)hipEventRecord(e0, st);
     {
-        Gs2mRange rg("gs2m:tsdf_touch");
+        StageTimer tm(t->events, t->timing != 0, st, 0, "gs2m:tsdf_touch");
         gs2m_launch_tsdf_touch(st, t->V, f, depth, mask);
     }
-    if (tm) {
-        (void)hipEventRecord(e1, st);
-        (void)hipEventRecord(e2, st);
-    }
-    // persistent grid: enough workgroups to fill the chip; each loops over the touched list
     {
-        Gs2mRange rg("gs2m:tsdf_integrate");
+        // persistent grid: enough workgroups to fill the chip; each loops over the touched list
+        StageTimer tm(t->events, t->timing != 0, st, 1, "gs2m:tsdf_integrate");
         gs2m_launch_tsdf_integrate(st, t->n_cu * 7, t->V, f, depth, color, mask);
-    }
-    if (tm) {
-        (void)hipEventRecord(e3, st);
-        t->events.push(0, e0, e1);
-        t->events.push(1, e2, e3);
     }
     return 0;
 }
@@ -309,10 +299,9 @@ extern "C" int gs2m_tsdf_integrate_batch(gs2m_tsdf* t, int n_frames, const float
         gs2m_set_error("[ScalableTSDFVolume::Integrate] Unsupported image format.");
         return 1;
     }
-    if (n_frames > 0 && (width <= 0 || height <= 0 || width > 65535 || height > 65535 || !(fx != 0) || !(fy != 0) || !(depth_scale != 0))) {
-        gs2m_set_error("gs2m_tsdf_integrate_batch: bad intrinsics / size (the sweep packs pixel coordinates in 16 bits: <= 65535)");
+    if (n_frames > 0 && check_frame_geometry("gs2m_tsdf_integrate_batch", width, height, fx, fy, depth_scale, 65535,
+                                             " (the sweep packs pixel coordinates in 16 bits: <= 65535)"))
         return 1;
-    }
     GS2M_HIPCHK(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
     for (int f0 = 0; f0 < n_frames; f0 += GS2M_TSDF_MAX_BATCH) {
@@ -340,31 +329,13 @@ extern "C" int gs2m_tsdf_integrate_batch(gs2m_tsdf* t, int n_frames, const float
         GS2M_HIPCHK(hipEventRecord(t->ring_done[slot], st));
         GS2M_HIPCHK(hipMemsetAsync(t->V.counters + 1, 0, sizeof(unsigned), st));  // touched_count = 0
         GS2M_HIPCHK(hipMemsetAsync(t->V.counters + 3, 0, sizeof(unsigned), st));  // work counter of the batch sweep
-        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-        if (t->timing) {
-            e0 = t->events.get();
-            e1 = t->events.get();
-            e2 = t->events.get();
-            e3 = t->events.get();
-        }
-        const bool tm = e0 && e1 && e2 && e3;
-        if (tm) (void)hipEventRecord(e0, st);
-        {
-            Gs2mRange rg("gs2m:tsdf_touch_batch");
+        {   // a batch counts as nf launches of each stage: the averages stay per frame
+            StageTimer tm(t->events, t->timing != 0, st, 0, "gs2m:tsdf_touch_batch", nf);
             gs2m_launch_tsdf_touch_batch(st, t->V, hb[0].f, nf, t->d_bframes.get());
         }
-        if (tm) {
-            (void)hipEventRecord(e1, st);
-            (void)hipEventRecord(e2, st);
-        }
         {
-            Gs2mRange rg("gs2m:tsdf_integrate_batch");
+            StageTimer tm(t->events, t->timing != 0, st, 1, "gs2m:tsdf_integrate_batch", nf);
             gs2m_launch_tsdf_integrate_batch(st, t->n_cu, t->V, t->d_bframes.get());
-        }
-        if (tm) {
-            (void)hipEventRecord(e3, st);
-            t->events.push(0, e0, e1, nf);
-            t->events.push(1, e2, e3, nf);
         }
     }
     return 0;

@@ -31,7 +31,7 @@ struct TsdfVolume {  // device pointers + sizes, passed by value
     unsigned* stamp;               // [hash_cap]  last frame id that touched the entry
     unsigned* touched;             // [hash_cap]  hash indices touched this frame / batch
     unsigned long long* fmask;     // [hash_cap]  batch mode: bit f = frame f of the batch touched the block (0 between batches)
-    unsigned* counters;            // [0] n_blocks  [1] touched_count  [2] overflow flags
+    unsigned* counters;            // [0] n_blocks  [1] touched_count  [2] overflow flags  [3] work counter of the batch sweep
     unsigned long long* totals;    // [0] block updates (sum over frames of touched blocks)
     unsigned hash_cap;             // power of two
     unsigned max_blocks;
@@ -71,6 +71,11 @@ GS2M_DEVICE unsigned long long tsdf_pack_key(int bx, int by, int bz) {
     return ((unsigned long long)(unsigned)(bx + GS2M_TSDF_KEY_BIAS) << 42) |
            ((unsigned long long)(unsigned)(by + GS2M_TSDF_KEY_BIAS) << 21) |
            (unsigned long long)(unsigned)(bz + GS2M_TSDF_KEY_BIAS);
+}
+GS2M_DEVICE void tsdf_unpack_key(unsigned long long key, int& bx, int& by, int& bz) {
+    bx = (int)((key >> 42) & 0x1fffffull) - GS2M_TSDF_KEY_BIAS;
+    by = (int)((key >> 21) & 0x1fffffull) - GS2M_TSDF_KEY_BIAS;
+    bz = (int)(key & 0x1fffffull) - GS2M_TSDF_KEY_BIAS;
 }
 GS2M_DEVICE bool tsdf_key_in_range(int bx, int by, int bz) {
     const int B = GS2M_TSDF_KEY_BIAS;

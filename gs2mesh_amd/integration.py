@@ -151,31 +151,38 @@ class ScalableTSDFVolume:
             return None
         return _lib.MEMORY.upload(a, dtype, self.device)
 
+    def _frame_to_dev(self, image, mask, intrinsic):
+        """``(image, mask)`` -> the device tensors ``(depth, color, mask)`` the kernels read (``color`` only for a volume
+        with colour, ``mask`` only when given), checked against ``intrinsic`` as Open3D checks them."""
+        f32 = torch.float32 if torch is not None else None
+        u8 = torch.uint8 if torch is not None else None
+        has_color = self.color_type == TSDFVolumeColorType.RGB8
+        depth = self._to_dev(image.depth, f32)
+        color = self._to_dev(image.color, u8) if has_color else None
+        msk = self._to_dev(mask, u8) if mask is not None else None
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        bad = W != intrinsic.width or H != intrinsic.height or depth.ndim != 2
+        if has_color:
+            bad = bad or color is None or color.ndim != 3 or tuple(color.shape) != (H, W, 3)
+        if bad:
+            raise RuntimeError("[ScalableTSDFVolume::Integrate] Unsupported image format.")
+        return depth, color, msk
+
     def integrate(self, image: RGBDImage, intrinsic: PinholeCameraIntrinsic, extrinsic, mask=None, min_depth=0.0,
                   stream=None):
         """``volume.integrate(rgbd, intrinsic, extrinsic_world_to_camera)``.  Extras (fused
         TSDF.run preprocessing, tsdf_utils.py:68-83): ``mask`` [H,W] (depth *= mask != 0) and
         ``min_depth`` (depth < min_depth -> 0), both applied before the scale/trunc conversion."""
-        f32 = torch.float32 if torch is not None else None
-        u8 = torch.uint8 if torch is not None else None
-        depth = self._to_dev(image.depth, f32)
-        color = self._to_dev(image.color, u8) if self.color_type == TSDFVolumeColorType.RGB8 else None
-        msk = self._to_dev(mask, u8) if mask is not None else None
+        depth, color, msk = self._frame_to_dev(image, mask, intrinsic)
         # buffers WE created (uploads / dtype conversions) must outlive the asynchronous kernels;
         # caller-owned device tensors are the caller's to keep alive until it synchronises
         ours = [t for t, src in ((depth, image.depth), (color, image.color), (msk, mask))
                 if t is not None and t is not src]
-        H, W = int(depth.shape[0]), int(depth.shape[1])
-        bad = (W != intrinsic.width or H != intrinsic.height or depth.ndim != 2)
-        if self.color_type == TSDFVolumeColorType.RGB8:
-            bad = bad or color is None or color.ndim != 3 or tuple(color.shape) != (H, W, 3)
-        if bad:
-            raise RuntimeError("[ScalableTSDFVolume::Integrate] Unsupported image format.")
         E = np.ascontiguousarray(np.asarray(extrinsic, np.float64).reshape(4, 4))
         st = _stream_of(depth, stream)
         _lib.check(self._lib.gs2m_tsdf_integrate(
-            self._h, _ptr(depth), _ptr(color), _ptr(msk), W, H, intrinsic.fx, intrinsic.fy, intrinsic.cx,
-            intrinsic.cy, E.ctypes.data_as(C.POINTER(C.c_double)), float(image.depth_scale),
+            self._h, _ptr(depth), _ptr(color), _ptr(msk), intrinsic.width, intrinsic.height, intrinsic.fx, intrinsic.fy,
+            intrinsic.cx, intrinsic.cy, E.ctypes.data_as(C.POINTER(C.c_double)), float(image.depth_scale),
             float(image.depth_trunc), float(min_depth), st), self._lib)
         self.frames_local += 1
         if ours:
@@ -192,22 +199,12 @@ class ScalableTSDFVolume:
             return
         if len(extrinsics) != n or (masks is not None and len(masks) != n):
             raise ValueError("integrate_batch: images / extrinsics / masks must have the same length")
-        f32 = torch.float32 if torch is not None else None
-        u8 = torch.uint8 if torch is not None else None
         has_color = self.color_type == TSDFVolumeColorType.RGB8
         keep, dp, cp, mp = [], (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
         for i, im in enumerate(images):
             if (im.depth_scale, im.depth_trunc) != (images[0].depth_scale, images[0].depth_trunc):
                 raise ValueError("integrate_batch: the frames of a batch share one depth_scale / depth_trunc")
-            d = self._to_dev(im.depth, f32)
-            c = self._to_dev(im.color, u8) if has_color else None
-            m = self._to_dev(masks[i], u8) if masks is not None and masks[i] is not None else None
-            H, W = int(d.shape[0]), int(d.shape[1])
-            bad = W != intrinsic.width or H != intrinsic.height or d.ndim != 2
-            if has_color:
-                bad = bad or c is None or c.ndim != 3 or tuple(c.shape) != (H, W, 3)
-            if bad:
-                raise RuntimeError("[ScalableTSDFVolume::Integrate] Unsupported image format.")
+            d, c, m = self._frame_to_dev(im, masks[i] if masks is not None else None, intrinsic)
             keep += [d, c, m]
             dp[i], cp[i], mp[i] = _ptr(d), _ptr(c), _ptr(m)
         E = np.ascontiguousarray(np.stack([np.asarray(e, np.float64).reshape(4, 4) for e in extrinsics]))

@@ -198,6 +198,18 @@ int main() {
         pool.push(0, r[2], r[3], 2);   // left live: the destructor destroys live and free events alike
         (void)hipEventDestroy(f);      // never pushed: not the pool's
     }
+    {   // the stage timer: a pair per timed stage, counted with its weight; nothing recorded when timing is off
+        EventPool pool;
+        hipStream_t st = nullptr;
+        { StageTimer tm(pool, true, st, 0, "check:touch", 3); }
+        { StageTimer tm(pool, true, st, 1, "check:integrate", 3); }
+        { StageTimer tm(pool, true, st, 1, "check:integrate"); }
+        { StageTimer tm(pool, false, st, 0, "check:off", 7); }
+        double ms[2] = {0.0, 0.0};
+        int64_t launches[2] = {0, 0};
+        pool.drain(ms, launches, 2);
+        CHECK(launches[0] == 3 && launches[1] == 4 && ms[0] >= 0.0 && ms[1] >= 0.0);
+    }
     if (g_failed) {
         printf("%d checks failed\n", g_failed);
         return 1;
