@@ -11,6 +11,23 @@
 
 GS2M_DEVICE int gs2m_imin(int a, int b) { return a < b ? a : b; }
 GS2M_DEVICE int gs2m_imax(int a, int b) { return a > b ? a : b; }
+// float -> int of the projection stage (radius, getRect, the exact-cull box): truncation toward zero, NaN -> 0, saturation at
+// INT_MIN / INT_MAX.  That is what the reference gets from its own hardware's conversion and what gfx950's v_cvt_i32_f32
+// does.  A C++ cast of a NaN or of an out-of-range float is undefined (x86 yields INT_MIN for all of them; a compiler may
+// fold around it), so neither form is a cast of such a value: the device form NAMES the instruction (the one the cast
+// compiles to: same code, defined result), the host / emulator form spells the cases out.  oracle/raster_oracle.c: f2i_sat.
+GS2M_DEVICE int gs2m_f2i_sat(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    int r;
+    asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+#else
+    if (!(x == x)) return 0;
+    if (x >= 2147483648.0f) return 2147483647;
+    if (x <= -2147483648.0f) return -2147483647 - 1;
+    return (int)x;
+#endif
+}
 
 // DGR/cuda_rasterizer/auxiliary.h:58-66 transformPoint4x3
 GS2M_DEVICE void xform4x3(const float* m, float x, float y, float z, float& ox, float& oy, float& oz) {

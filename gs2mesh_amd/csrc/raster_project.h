@@ -82,13 +82,15 @@ GS2M_DEVICE void project_view(const CamUniform& cam, float px, float py, float p
     const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
     o.mx = ndc2pix(ppx, cam.W);
     o.my = ndc2pix(ppy, cam.H);
-    const int r = (int)my_radius;
+    // Non-finite / overflowing input (DESIGN.md "Parity"): every float -> int below is gs2m_f2i_sat (NaN -> 0, saturating).
+    const int r = gs2m_f2i_sat(my_radius);
     // auxiliary.h:46-56 getRect
-    o.x0 = gs2m_imin(cam.gx, gs2m_imax(0, (int)((o.mx - r) / GS2M_TILE)));
-    o.y0 = gs2m_imin(cam.gy, gs2m_imax(0, (int)((o.my - r) / GS2M_TILE)));
-    o.x1 = gs2m_imin(cam.gx, gs2m_imax(0, (int)((o.mx + r + GS2M_TILE - 1) / GS2M_TILE)));
-    o.y1 = gs2m_imin(cam.gy, gs2m_imax(0, (int)((o.my + r + GS2M_TILE - 1) / GS2M_TILE)));
-    if ((o.x1 - o.x0) * (o.y1 - o.y0) == 0) {
+    o.x0 = gs2m_imin(cam.gx, gs2m_imax(0, gs2m_f2i_sat((o.mx - r) / GS2M_TILE)));
+    o.y0 = gs2m_imin(cam.gy, gs2m_imax(0, gs2m_f2i_sat((o.my - r) / GS2M_TILE)));
+    o.x1 = gs2m_imin(cam.gx, gs2m_imax(0, gs2m_f2i_sat((o.mx + r + GS2M_TILE - 1) / GS2M_TILE)));
+    o.y1 = gs2m_imin(cam.gy, gs2m_imax(0, gs2m_f2i_sat((o.my + r + GS2M_TILE - 1) / GS2M_TILE)));
+    // r <= 0 (a NaN radius; the reference emits no instance for radii == 0, rasterizer_impl.cu:85): invisible, as radius 0 says
+    if (r <= 0 || (o.x1 - o.x0) * (o.y1 - o.y0) == 0) {
         o.x0 = o.y0 = o.x1 = o.y1 = 0;
         return;
     }
@@ -326,10 +328,11 @@ GS2M_DEVICE void project_gaussian(const GaussIn& g, const CamUniform* __restrict
                     } else {
                         const float hx = sqrtf(2.0f * thr * pv[v].cova) + 0.01f;
                         const float hy = sqrtf(2.0f * thr * pv[v].covc) + 0.01f;
-                        const int bx0 = (int)ceilf((pv[v].mx - hx - (float)(GS2M_TILE - 1)) / GS2M_TILE);
-                        const int bx1 = (int)floorf((pv[v].mx + hx) / GS2M_TILE) + 1;
-                        const int by0 = (int)ceilf((pv[v].my - hy - (float)(GS2M_TILE - 1)) / GS2M_TILE);
-                        const int by1 = (int)floorf((pv[v].my + hy) / GS2M_TILE) + 1;
+                        // the + 1 in float: exact wherever the box can bind (|tiles| < 2^24), and no int overflow at +inf
+                        const int bx0 = gs2m_f2i_sat(ceilf((pv[v].mx - hx - (float)(GS2M_TILE - 1)) / GS2M_TILE));
+                        const int bx1 = gs2m_f2i_sat(floorf((pv[v].mx + hx) / GS2M_TILE) + 1.0f);
+                        const int by0 = gs2m_f2i_sat(ceilf((pv[v].my - hy - (float)(GS2M_TILE - 1)) / GS2M_TILE));
+                        const int by1 = gs2m_f2i_sat(floorf((pv[v].my + hy) / GS2M_TILE) + 1.0f);
                         pv[v].x0 = gs2m_imax(pv[v].x0, bx0);
                         pv[v].y0 = gs2m_imax(pv[v].y0, by0);
                         pv[v].x1 = gs2m_imin(pv[v].x1, bx1);

@@ -70,11 +70,11 @@ def raster_lib():
         lib.oracle_preprocess.restype = None
         lib.oracle_preprocess.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, vp, vp, vp,
                                           vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float,
-                                          vp, vp, vp, vp, vp, vp, vp, vp]
+                                          vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.oracle_mark_visible.restype = None
         lib.oracle_mark_visible.argtypes = [C.c_int, vp, vp, vp, vp]
         lib.oracle_bin.restype = C.c_int64
-        lib.oracle_bin.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int64]
+        lib.oracle_bin.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp, vp]
         lib.oracle_render.restype = None
         lib.oracle_render.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.oracle_rasterize_forward.restype = C.c_int64
@@ -143,13 +143,13 @@ def preprocess(means3D, scales, rotations, opacities, shs, viewmatrix, projmatri
         radii=np.zeros(P, np.int32), means2D=np.zeros((P, 2), np.float32), depths=np.zeros(P, np.float32),
         cov3D=np.zeros((P, 6), np.float32), rgb=np.zeros((P, 3), np.float32),
         conic_opacity=np.zeros((P, 4), np.float32), tiles_touched=np.zeros(P, np.uint32),
-        rect=np.zeros((P, 4), np.uint32))
+        rect=np.zeros((P, 4), np.uint32), cov2D=np.zeros((P, 2), np.float32))
     lib.oracle_preprocess(P, sh_degree, M, _ptr(means3D), _ptr(scales), float(scale_modifier), _ptr(rotations),
                           _ptr(opacities), _ptr(shs), _ptr(cov3D_precomp), _ptr(colors_precomp), _ptr(vm),
                           _ptr(pm), _ptr(cp), int(W), int(H), float(tanfovx), float(tanfovy),
                           _ptr(out["radii"]), _ptr(out["means2D"]), _ptr(out["depths"]), _ptr(out["cov3D"]),
                           _ptr(out["rgb"]), _ptr(out["conic_opacity"]), _ptr(out["tiles_touched"]),
-                          _ptr(out["rect"]))
+                          _ptr(out["rect"]), _ptr(out["cov2D"]))
     return out
 
 
@@ -164,17 +164,22 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     return present.astype(bool)
 
 
-def bin_instances(geom, W, H, exact_cull=False):
-    """duplicateWithKeys + stable sort + identifyTileRanges -> (point_list[n], ranges[tiles,2])."""
+def bin_instances(geom, W, H, exact_cull=False, want_rect=False):
+    """duplicateWithKeys + stable sort + identifyTileRanges -> (point_list[n], ranges[tiles,2]).  ``exact_cull`` 1 / 2: the
+    kernel's culled lists; the cull box comes from ``geom["cov2D"]`` (``preprocess``) where the record has it, from the inverse
+    of the conic otherwise.  ``want_rect``: also the rect [P,4] each Gaussian is binned with (all zero: none)."""
     lib = raster_lib()
     P = geom["radii"].shape[0]
     cap = int(geom["tiles_touched"].astype(np.int64).sum())
     pl = np.zeros(max(cap, 1), np.uint32)
     gx, gy = (W + 15) // 16, (H + 15) // 16
     ranges = np.zeros((gx * gy, 2), np.uint32)
+    cov2D = geom.get("cov2D")
+    rect = np.zeros((P, 4), np.uint32) if want_rect else None
     n = lib.oracle_bin(P, W, H, _ptr(geom["radii"]), _ptr(geom["means2D"]), _ptr(geom["depths"]),
-                       _ptr(geom["conic_opacity"]), int(exact_cull), _ptr(pl), _ptr(ranges), cap)
-    return pl[:n].copy(), ranges
+                       _ptr(geom["conic_opacity"]), int(exact_cull), _ptr(pl), _ptr(ranges), cap,
+                       None if cov2D is None else _ptr(np.ascontiguousarray(cov2D, np.float32)), _ptr(rect))
+    return (pl[:n].copy(), ranges, rect) if want_rect else (pl[:n].copy(), ranges)
 
 
 def render(W, H, ranges, point_list, means2D, features, conic_opacity, bg):

@@ -54,13 +54,23 @@ static float ndc2Pix(float v, int S) { return (float)(((v + 1.0) * S - 1.0) * 0.
 static int imin(int a, int b) { return a < b ? a : b; }
 static int imax(int a, int b) { return a > b ? a : b; }
 
+/* The reference's float -> int conversions run on its own hardware: truncation toward zero, NaN -> 0, saturation at
+ * INT_MIN / INT_MAX (cvt.rzi.s32.f32).  A C cast of a NaN or of an out-of-range float is undefined (x86: INT_MIN), so the
+ * conversion is spelled out; same function as gs2m_f2i_sat (gs2mesh_amd/csrc/raster_math.h). */
+static int f2i_sat(float x) {
+    if (!(x == x)) return 0;
+    if (x >= 2147483648.0f) return INT32_MAX;
+    if (x <= -2147483648.0f) return INT32_MIN;
+    return (int)x;
+}
+
 /* auxiliary.h:46-56 -- (int) casts truncate toward zero; max_radius is int */
 static void getRect(float px, float py, int max_radius, int gx, int gy, uint32_t* rmin,
                     uint32_t* rmax) {
-    rmin[0] = (uint32_t)imin(gx, imax(0, (int)((px - max_radius) / BLOCK_X)));
-    rmin[1] = (uint32_t)imin(gy, imax(0, (int)((py - max_radius) / BLOCK_Y)));
-    rmax[0] = (uint32_t)imin(gx, imax(0, (int)((px + max_radius + BLOCK_X - 1) / BLOCK_X)));
-    rmax[1] = (uint32_t)imin(gy, imax(0, (int)((py + max_radius + BLOCK_Y - 1) / BLOCK_Y)));
+    rmin[0] = (uint32_t)imin(gx, imax(0, f2i_sat((px - max_radius) / BLOCK_X)));
+    rmin[1] = (uint32_t)imin(gy, imax(0, f2i_sat((py - max_radius) / BLOCK_Y)));
+    rmax[0] = (uint32_t)imin(gx, imax(0, f2i_sat((px + max_radius + BLOCK_X - 1) / BLOCK_X)));
+    rmax[1] = (uint32_t)imin(gy, imax(0, f2i_sat((py + max_radius + BLOCK_Y - 1) / BLOCK_Y)));
 }
 
 /* auxiliary.h:58-66 */
@@ -199,7 +209,8 @@ static void computeCov2D(const float* mean, float focal_x, float focal_y, float 
  * preprocessCUDA (forward.cu:155-256) for all P Gaussians of one view.
  * Outputs (all caller-allocated, size P unless noted; zero-initialised here where the
  * reference initialises): radii[P], means2D[P,2], depths[P], cov3D[P,6], rgb[P,3],
- * conic_opacity[P,4], tiles_touched[P], rect[P,4] (x0,y0,x1,y1; extra, for tests).
+ * conic_opacity[P,4], tiles_touched[P], rect[P,4] (x0,y0,x1,y1; extra, for tests), cov2D[P,2] (cov.xx, cov.yy of the
+ * EWA projection; extra, may be NULL: what the exact-cull box of oracle_bin is formed from).
  * Entries of skipped Gaussians keep whatever the caller put there except radii and
  * tiles_touched (set to 0), as in the reference.
  */
@@ -209,7 +220,7 @@ void oracle_preprocess(int P, int D, int M, const float* orig_points, const floa
                        const float* viewmatrix, const float* projmatrix, const float* cam_pos,
                        int W, int H, float tan_fovx, float tan_fovy, int* radii, float* means2D,
                        float* depths, float* cov3Ds, float* rgb, float* conic_opacity,
-                       uint32_t* tiles_touched, uint32_t* rect) {
+                       uint32_t* tiles_touched, uint32_t* rect, float* cov2D) {
     /* rasterizer_impl.cu:222-223 */
     const float focal_y = H / (2.0f * tan_fovy);
     const float focal_x = W / (2.0f * tan_fovx);
@@ -247,19 +258,28 @@ void oracle_preprocess(int P, int D, int M, const float* orig_points, const floa
         float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
         float px = ndc2Pix(p_proj[0], W), py = ndc2Pix(p_proj[1], H);
         uint32_t rmin[2], rmax[2];
-        getRect(px, py, (int)my_radius, gx, gy, rmin, rmax);
+        const int radius = f2i_sat(my_radius);
+        getRect(px, py, radius, gx, gy, rmin, rmax);
+        /* radius <= 0 (a NaN radius converts to 0): the reference would count the rect's tiles here and then emit no key for
+         * them (duplicateWithKeys: radii > 0), leaving entries of its list unwritten.  Such a splat is invisible, as its
+         * radius says: no rect, no tiles. */
+        if (radius <= 0) continue;
         if ((rmax[0] - rmin[0]) * (rmax[1] - rmin[1]) == 0) continue;
         if (!colors_precomp) {
             computeColorFromSH(idx, D, M, orig_points, cam_pos, shs, rgb + 3 * (size_t)idx);
         }
         depths[idx] = p_view[2];
-        radii[idx] = (int)my_radius;
+        radii[idx] = radius;
         means2D[2 * idx] = px;
         means2D[2 * idx + 1] = py;
         conic_opacity[4 * idx + 0] = conic[0];
         conic_opacity[4 * idx + 1] = conic[1];
         conic_opacity[4 * idx + 2] = conic[2];
         conic_opacity[4 * idx + 3] = opacities[idx];
+        if (cov2D) {
+            cov2D[2 * idx] = cov[0];
+            cov2D[2 * idx + 1] = cov[2];
+        }
         tiles_touched[idx] = (rmax[1] - rmin[1]) * (rmax[0] - rmin[0]);
         if (rect) {
             rect[4 * idx + 0] = rmin[0];
@@ -309,10 +329,14 @@ int oracle_tile_may_contribute(float mx, float my, float ca, float cb, float cc,
  * and ranges[2*tiles] (zeroed first, rasterizer_impl.cu:310).
  * exact_cull != 0 applies oracle_tile_may_contribute (extension, see above): 1 = to every rect with corners (>= 2 x 2 tiles),
  * 2 = only to those of more than 4 tiles.
+ * cov2D[P,2] (oracle_preprocess): the box is formed from the projected covariance, as the kernel forms it (raster_project.h) --
+ * the same arithmetic, NaN and inf included.  NULL (a record that carries no covariance: oracle/parity.py,
+ * compositing_attribution): cov = conic^-1, equal to rounding for finite input.
+ * rect_out[P,4] (may be NULL): the rect each Gaussian is binned with (all zero: none) -- what the kernel stores.
  */
 int64_t oracle_bin(int P, int W, int H, const int* radii, const float* means2D,
                    const float* depths, const float* conic_opacity, int exact_cull,
-                   uint32_t* point_list, uint32_t* ranges, int64_t capacity) {
+                   uint32_t* point_list, uint32_t* ranges, int64_t capacity, const float* cov2D, uint32_t* rect_out) {
     const int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
     int64_t n = 0;
     for (int idx = 0; idx < P; ++idx) {
@@ -324,6 +348,7 @@ int64_t oracle_bin(int P, int W, int H, const int* radii, const float* means2D,
     }
     kv_t* kv = (kv_t*)malloc(sizeof(kv_t) * (size_t)(n > 0 ? n : 1));
     int64_t off = 0;
+    if (rect_out) memset(rect_out, 0, sizeof(uint32_t) * 4 * (size_t)P);
     for (int idx = 0; idx < P; ++idx) {
         if (radii[idx] > 0) {
             uint32_t rmin[2], rmax[2];
@@ -337,13 +362,14 @@ int64_t oracle_bin(int P, int W, int H, const int* radii, const float* means2D,
                 if (!(op * 255.0f >= 1.0f)) continue;
                 const float thr = logf(op * 255.0f) * 1.0001f + 0.001f;
                 const float detc = ca * cc - cb * cb;
-                const float cova = cc / detc, covc = ca / detc; /* cov = conic^-1 */
+                const float cova = cov2D ? cov2D[2 * idx] : cc / detc;     /* cov.xx, cov.yy: the kernel's, or conic^-1 */
+                const float covc = cov2D ? cov2D[2 * idx + 1] : ca / detc;
                 const float hx = sqrtf(2.0f * thr * cova) + 0.01f, hy = sqrtf(2.0f * thr * covc) + 0.01f;
                 const float mx = means2D[2 * idx], my = means2D[2 * idx + 1];
-                const int bx0 = (int)ceilf((mx - hx - (float)(BLOCK_X - 1)) / BLOCK_X);
-                const int bx1 = (int)floorf((mx + hx) / BLOCK_X) + 1;
-                const int by0 = (int)ceilf((my - hy - (float)(BLOCK_Y - 1)) / BLOCK_Y);
-                const int by1 = (int)floorf((my + hy) / BLOCK_Y) + 1;
+                const int bx0 = f2i_sat(ceilf((mx - hx - (float)(BLOCK_X - 1)) / BLOCK_X));
+                const int bx1 = f2i_sat(floorf((mx + hx) / BLOCK_X) + 1.0f);
+                const int by0 = f2i_sat(ceilf((my - hy - (float)(BLOCK_Y - 1)) / BLOCK_Y));
+                const int by1 = f2i_sat(floorf((my + hy) / BLOCK_Y) + 1.0f);
                 if ((int)rmin[0] < bx0) rmin[0] = (uint32_t)bx0;
                 if ((int)rmin[1] < by0) rmin[1] = (uint32_t)by0;
                 if ((int)rmax[0] > bx1) rmax[0] = (uint32_t)(bx1 < 0 ? 0 : bx1);
@@ -352,6 +378,12 @@ int64_t oracle_bin(int P, int W, int H, const int* radii, const float* means2D,
                 per_tile = (rmax[0] - rmin[0]) >= 2 && (rmax[1] - rmin[1]) >= 2;
                 /* level 2 (round 6): rects of at most 4 tiles keep all their tiles (gs2m_rect_tested, raster_project.h) */
                 if (exact_cull == 2 && (rmax[0] - rmin[0]) * (rmax[1] - rmin[1]) <= 4) per_tile = 0;
+            }
+            if (rect_out) {
+                rect_out[4 * idx] = rmin[0];
+                rect_out[4 * idx + 1] = rmin[1];
+                rect_out[4 * idx + 2] = rmax[0];
+                rect_out[4 * idx + 3] = rmax[1];
             }
             for (uint32_t y = rmin[1]; y < rmax[1]; y++) {
                 for (uint32_t x = rmin[0]; x < rmax[0]; x++) {
@@ -532,16 +564,17 @@ int64_t oracle_rasterize_forward(int P, int D, int M, const float* background, i
     float* rgb = (float*)calloc((size_t)P * 3, sizeof(float));
     float* conic_opacity = (float*)calloc((size_t)P * 4, sizeof(float));
     uint32_t* tiles_touched = (uint32_t*)calloc((size_t)P, sizeof(uint32_t));
+    float* cov2D = (float*)calloc((size_t)P * 2, sizeof(float));
     oracle_preprocess(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
                       cov3D_precomp, colors_precomp, viewmatrix, projmatrix, cam_pos, W, H,
                       tan_fovx, tan_fovy, radii, means2D, depths, cov3Ds, rgb, conic_opacity,
-                      tiles_touched, NULL);
+                      tiles_touched, NULL, cov2D);
     int64_t n_ref = 0;
     for (int i = 0; i < P; ++i) n_ref += tiles_touched[i];
     uint32_t* point_list = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(n_ref > 0 ? n_ref : 1));
     uint32_t* ranges = (uint32_t*)malloc(sizeof(uint32_t) * 2 * (size_t)gx * gy);
     int64_t n = oracle_bin(P, W, H, radii, means2D, depths, conic_opacity, exact_cull,
-                           point_list, ranges, n_ref);
+                           point_list, ranges, n_ref, cov2D, NULL);
     const float* feat = colors_precomp ? colors_precomp : rgb;
     oracle_render(W, H, ranges, point_list, means2D, feat, conic_opacity, background, out_color,
                   NULL, NULL);
@@ -553,6 +586,7 @@ int64_t oracle_rasterize_forward(int P, int D, int M, const float* background, i
     free(rgb);
     free(conic_opacity);
     free(tiles_touched);
+    free(cov2D);
     free(point_list);
     free(ranges);
     return n;
