@@ -33,6 +33,13 @@ class Gaussians(C.Structure):
                 ("xyz", vp), ("scales", vp), ("rotations", vp), ("opacities", vp), ("shs", vp), ("shs_rest", vp)]
 
 
+class AdamSegment(C.Structure):
+    """gs2m_adam_segment (host struct of device pointers and the scalars of one tensor's Adam step)."""
+    _fields_ = [("param", vp), ("grad", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("count", C.c_int64), ("step", C.c_int64),
+                ("row_width", C.c_int32), ("reserved", C.c_int32), ("lr", f64), ("beta1", f64), ("beta2", f64), ("eps", f64)]
+
+
+ADAM_MAX_SEGMENTS = 8
 ABI_VERSION = 600   # GS2M_VERSION of include/gs2mesh_amd.h this binding was written against
 OPT_EXACT_TILE_CULL = 1
 OPT_BLEND_VARIANT = 2
@@ -88,6 +95,8 @@ _PROTOS = {
     "gs2m_photo_loss_scratch_bytes": (i64, [i32, i32, i32]),
     "gs2m_photo_loss_forward": (i32, [i32, i32, i32, vp, vp, f32, vp, i64, vp, vp, vp, vp]),
     "gs2m_photo_loss_backward": (i32, [i32, i32, i32, vp, vp, vp, f32, vp, vp, vp]),
+    "gs2m_adam_step": (i32, [i32, C.POINTER(AdamSegment), vp, i64, vp]),
+    "gs2m_densify_stats": (i32, [i32, vp, vp, vp, vp, vp, vp]),
     "gs2m_mask_preprocess": (i32, [i32, i32, i32, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, C.POINTER(vp), vp, vp]),
     "gs2m_tsdf_create": (i32, [C.POINTER(vp), f64, f64, i32, i32, i32, i64, i32]),
     "gs2m_tsdf_destroy": (i32, [vp]),

@@ -262,7 +262,14 @@ class GaussianModel:
         lr = {"xyz": a.position_lr_init * self.spatial_lr_scale, "f_dc": a.feature_lr, "f_rest": a.feature_lr / 20.0,
               "opacity": a.opacity_lr, "scaling": a.scaling_lr, "rotation": a.rotation_lr}
         groups = [{"params": [getattr(self, attr)], "lr": lr[name], "name": name} for name, attr in _GROUPS]
-        self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        kind = getattr(a, "optimizer_type", "default")
+        if kind == "default":
+            self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        elif kind in ("fused", "sparse_adam"):
+            from .optim import FusedAdam
+            self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)
+        else:
+            raise ValueError(f"optimizer_type must be 'default', 'fused' or 'sparse_adam', got {kind!r}")
         self.xyz_scheduler_args = get_expon_lr_func(lr_init=a.position_lr_init * self.spatial_lr_scale,
                                                     lr_final=a.position_lr_final * self.spatial_lr_scale,
                                                     lr_delay_mult=a.position_lr_delay_mult,
@@ -392,3 +399,11 @@ class GaussianModel:
         self.xyz_gradient_accum[update_filter] += torch.norm(viewspace_point_tensor.grad[update_filter, :2], dim=-1,
                                                              keepdim=True)
         self.denom[update_filter] += 1
+
+    def update_densification_stats(self, viewspace_point_tensor, radii):
+        """``max_radii2D[visible] = max(...)`` of the loop and ``add_densification_stats`` as one kernel
+        (``gs2m_densify_stats``) over the rows with ``radii > 0``; no mask is materialised and the host does not wait."""
+        from .optim import densify_stats
+        grad = viewspace_point_tensor.grad
+        densify_stats(radii, grad if grad.is_contiguous() else grad.contiguous(), self.max_radii2D, self.xyz_gradient_accum,
+                      self.denom)

@@ -63,6 +63,7 @@ class OptimizationParams:
         self.densify_until_iter = 15_000
         self.densify_grad_threshold = 0.0002
         self.random_background = False
+        self.optimizer_type = "default"     # "fused" / "sparse_adam": optim.FusedAdam, dense or on the visible rows only
         for k, v in overrides.items():
             if not hasattr(self, k):
                 raise TypeError(f"OptimizationParams has no parameter {k!r}")
@@ -220,11 +221,17 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
     background.  ``callback(iteration, event, gaussians, counts)`` is called after every densification (``"densify"``, with the
     ``{"cloned", "split", "pruned"}`` counts of ``densify_and_prune``) and opacity reset (``"reset_opacity"``, None).  ``timing``: None, or a dict that receives the stream time in ms of the four phases of
     every iteration (lists under ``render``, ``loss``, ``backward``, ``update``), measured with events and read at the end.
-    ``loss``: ``"torch"`` (``loss_fn``, the default) or ``"fused"`` (``fused_loss``, the HIP kernels)."""
+    ``loss``: ``"torch"`` (``loss_fn``, the default) or ``"fused"`` (``fused_loss``, the HIP kernels).  With
+    ``opt.optimizer_type`` ``"fused"`` or ``"sparse_adam"`` (``gaussians.optimizer`` is then an ``optim.FusedAdam``) the
+    densification statistics and the step are one kernel each, and an iteration that neither densifies nor resets opacity
+    has no host wait in its update phase; ``"sparse_adam"`` steps only the rows the view saw (``radii > 0``)."""
     if loss not in ("torch", "fused"):
         raise ValueError(f"train: loss must be 'torch' or 'fused', got {loss!r}")
     from .gaussian_renderer import render
     loss_of = fused_loss if loss == "fused" else loss_fn
+    from .optim import FusedAdam
+    native_update = isinstance(gaussians.optimizer, FusedAdam)
+    sparse = native_update and getattr(opt, "optimizer_type", "default") == "sparse_adam"
     rng = random.Random(seed)
     pipe = PipelineParams()
     losses = []
@@ -260,8 +267,11 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
         with torch.no_grad():
             losses.append(loss.detach())
             if iteration < opt.densify_until_iter:
-                gaussians.max_radii2D[visible] = torch.max(gaussians.max_radii2D[visible], radii[visible].to(gaussians.max_radii2D.dtype))
-                gaussians.add_densification_stats(viewspace, visible)
+                if native_update:
+                    gaussians.update_densification_stats(viewspace, radii)
+                else:
+                    gaussians.max_radii2D[visible] = torch.max(gaussians.max_radii2D[visible], radii[visible].to(gaussians.max_radii2D.dtype))
+                    gaussians.add_densification_stats(viewspace, visible)
                 if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
                     size_threshold = 20 if iteration > opt.opacity_reset_interval else None
                     counts = gaussians.densify_and_prune(opt.densify_grad_threshold, 0.005, extent, size_threshold)
@@ -272,7 +282,10 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
                     if callback:
                         callback(iteration, "reset_opacity", gaussians, None)
             if iteration < opt.iterations:
-                gaussians.optimizer.step()
+                if native_update:
+                    gaussians.optimizer.step(visible=radii if sparse else None)
+                else:
+                    gaussians.optimizer.step()
                 gaussians.optimizer.zero_grad(set_to_none=True)
         if t:
             t.append(mark())

@@ -37,7 +37,7 @@ extern "C" {
                             (gs2m_tsdf_flags_device, GS2M_OPT_BIN_LANE_TILES, GS2M_OPT_PROJECT_SHARED_READ, GS2M_OPT_EXACT_TILE_CULL level 2; GS2M_OPT_BLEND_MODE 1
                             removed).  Added since without a new number: gs2m_stereo_sgm / gs2m_stereo_sgm_scratch_bytes,
                             gs2m_knn_mean_dist2 / gs2m_knn_scratch_bytes, gs2m_photo_loss_forward / _backward /
-                            _scratch_bytes.  The Python binding checks it at load time */
+                            _scratch_bytes, gs2m_adam_step, gs2m_densify_stats.  The Python binding checks it at load time */
 
 typedef void* gs2m_stream; /* hipStream_t */
 
@@ -689,6 +689,97 @@ int gs2m_photo_loss_forward(int planes, int height, int width, const float* imag
                             void* scratch, int64_t scratch_bytes, float* out, float* partials, float* tap_map, gs2m_stream stream);
 int gs2m_photo_loss_backward(int planes, int height, int width, const float* image, const float* target, const float* partials,
                              float lambda_dssim, const float* grad_loss, float* grad_image, gs2m_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* training update: Adam step over several tensors, densification statistics            */
+/* ------------------------------------------------------------------------------------ */
+
+/*
+ * One Adam step (Kingma & Ba; the update torch.optim.Adam makes with amsgrad, weight decay and maximize off) of up to 8
+ * "segments" in ONE kernel launch.  A segment is a contiguous f32 tensor with its gradient, its two moments and its own
+ * scalars; t = step is the number of the step being taken (1 for the first).  Defined operation by operation in f32, every
+ * operation rounded on its own (no FMA), IEEE division and square root, subnormals kept (never flushed), parentheses = order:
+ *   - on the host, in double, cast to f32 last:  ss = f32(lr / (1 - beta1^t)),  bs = f32(sqrt(1 - beta2^t)),
+ *     omb1 = f32(1 - beta1),  b2 = f32(beta2),  omb2 = f32(1 - beta2),  e = f32(eps);  beta^t is pow(beta, (double)t);
+ *   - m' = m + omb1 * (g - m)
+ *   - v' = b2 * v + (omb2 * g) * g
+ *   - p' = p - ss * (m' / (sqrt(v') / bs + e))
+ * with p = param, g = grad, m = exp_avg, v = exp_avg_sq, updated in place.  One lane owns each element and nothing is
+ * accumulated across elements: the same bits on every run.  Special values follow from the operations: g = 0 with m = v = 0
+ * gives 0 / e = 0 and leaves p; |g| = 1e-20 gives the subnormal (omb2 * g) * g = 1e-43 (the product g * g is never formed); for
+ * the same reason |g| = 1e20, whose square overflows, gives the finite 1e37 and an ordinary step; from |g| of about 5.8e20 on
+ * (at beta2 = 0.999) v' overflows to +inf, the quotient is 0 and p stays, on that step and on those after it; a NaN or
+ * infinite g makes p NaN.
+ * tests/adam_statement.py restates this in numpy and the kernel agrees with it bit for bit on both back-ends.
+ *
+ * Distance of this form from the two usual evaluations, measured on the CPU with the numpy statement (200 000 elements,
+ * p ~ N(0, 1), gradients N(0, 1) * 10^U(-8, 0) with a third of them exactly 0 every seventh step, from m = v = 0; three seeds
+ * times (lr, eps, betas) = (0.0025, 1e-15, 0.9 / 0.999), (0.05, ...), (0.00016, ...), (0.001, 1e-8, 0.8 / 0.99)).  The unit is
+ * u(T) = ulp(p) + T * lr * 2^-23 for T steps: the rounding of p plus the rounding of T steps of size about lr (p may have been
+ * up to T * lr larger in magnitude on the way, with the larger ulp that goes with it).  Largest |p - yardstick| / u(T):
+ *   against Adam evaluated in double (torch's formulas) from the same f32 state, one step, t = 1 .. 50:      2.13
+ *   against torch.optim.Adam(foreach=False) on CPU tensors, first step:                                     1.20
+ *   50 carried steps against Adam carried in double:                                                        11.8
+ *   50 carried steps against torch.optim.Adam(foreach=False) carried in f32:                                2.40
+ * Stated tolerances, the measurements x 4 for inputs not tried, rounded up: GS2M_ADAM_TOL_FP64_STEP = 9, _TORCH_STEP = 5 (in
+ * u(1)), GS2M_ADAM_TOL_FP64_50 = 48, _TORCH_50 = 10 (in u(50)).  The form is not bit-equal to torch (no single-rounding
+ * formula is: torch's own CPU and GPU paths differ from each other).
+ *
+ * Row-sparse mode (row_visible != NULL): every segment is [rows][row_width]; element e belongs to row e / row_width and
+ * is updated only where row_visible[row] > 0 (the rasteriser's radii serve as the mask).  Elements of the other rows are
+ * neither read nor written: p, m and v keep their bits and their gradient entries may hold anything.  The arithmetic and the
+ * scalars are the same as above: the bias correction is that of `step`, not of a per-row count, and the moments of an unseen
+ * row do not decay.  With every row visible the call equals the dense call bit for bit.
+ *
+ *   n_segments, segments    1 .. 8; a HOST array, read before the call returns.  Segments with count == 0 are skipped; with
+ *                           every count 0 nothing is launched
+ *   param, grad, exp_avg,   device, count f32 each.  16-byte aligned pointers are moved 16 bytes per lane; others work,
+ *   exp_avg_sq              4 bytes at a time.  No two ranges of the call may overlap (row_visible included)
+ *   row_width               >= 1; used in row-sparse mode, where count must be rows * row_width
+ *   step                    >= 1;  betas in [0, 1)
+ *   row_visible, rows       NULL, or [rows] int32 device
+ * Stateless, asynchronous on `stream`, no allocation, no copy.  n_segments outside 1 .. 8, a NULL pointer with count > 0,
+ * a negative count, row_width < 1, step < 1, a beta outside [0, 1), a count that is not rows * row_width, overlapping ranges
+ * and a call of more than 2^31 - 1 workgroups of 1024 elements return 1 with gs2m_last_error(); nothing is written then.
+ */
+#define GS2M_ADAM_MAX_SEGMENTS 8
+#define GS2M_ADAM_TOL_FP64_STEP 9.0
+#define GS2M_ADAM_TOL_TORCH_STEP 5.0
+#define GS2M_ADAM_TOL_FP64_50 48.0
+#define GS2M_ADAM_TOL_TORCH_50 10.0
+typedef struct gs2m_adam_segment {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t count;
+    int64_t step;
+    int32_t row_width;
+    int32_t reserved; /* 0 */
+    double lr, beta1, beta2, eps;
+} gs2m_adam_segment;
+int gs2m_adam_step(int n_segments, const gs2m_adam_segment* segments, const int32_t* row_visible, int64_t rows,
+                   gs2m_stream stream);
+
+/*
+ * The densification statistics of one training iteration (GS/train.py:113-115, gaussian_model.py:405-407), one Gaussian per
+ * lane.  Where radii[i] > 0, every operation one f32 operation rounded on its own, IEEE square root:
+ *   r = (float)radii[i];  max_radii2D[i] = r > max_radii2D[i] ? r : max_radii2D[i]
+ *   n = sqrt(gx * gx + gy * gy), (gx, gy) = viewspace_grad[i][0 .. 1];  grad_accum[i] = grad_accum[i] + n;
+ *   denom[i] = denom[i] + 1
+ * Rows with radii[i] <= 0 are neither read (beyond radii) nor written.  denom and max_radii2D equal the torch ops of the
+ * reference's loop exactly.  n carries three roundings and torch.norm over the two columns at least one: they differ by at
+ * most 2 ulp(n), and after the addition to grad_accum >= n by at most 2 ulp(n) + 1 ulp(grad_accum) <= 3 ulp(grad_accum) =
+ * GS2M_DENSIFY_ACCUM_TOL_ULP per update.  Measured on the CPU over 100 000 rows of N(0, 1) * 10^U(-8, 0): n 1 ulp, grad_accum 2.
+ *   P                       0 does nothing and returns 0
+ *   radii                   [P] int32 device
+ *   viewspace_grad          [P][3] f32 device
+ *   max_radii2D, grad_accum, denom   [P] f32 device, updated in place
+ * Stateless, asynchronous on `stream`; a negative P or a NULL pointer returns 1 with gs2m_last_error().
+ */
+#define GS2M_DENSIFY_ACCUM_TOL_ULP 3
+int gs2m_densify_stats(int P, const int32_t* radii, const float* viewspace_grad, float* max_radii2D, float* grad_accum,
+                       float* denom, gs2m_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* PNG encoder (the Renderer's left.png / right.png)               */

@@ -1,13 +1,16 @@
 """Train a Gaussian splat on one GPU: point cloud + posed images -> point_cloud/iteration_N/point_cloud.ply.
 
     python tools/train_splat.py <colmap_dir> <out_dir> [--iterations N] [--resolution-scale s] [--loss {torch,fused}]
-    python tools/train_splat.py --synthetic <out_dir> [--iterations N] [--loss {torch,fused}]
+                                [--optimizer {default,fused,sparse_adam}]
+    python tools/train_splat.py --synthetic <out_dir> [--iterations N] [--loss {torch,fused}] [--optimizer ...]
 
 <colmap_dir> holds a COLMAP text model (sparse/0/cameras.txt, images.txt, points3D.txt; PINHOLE or SIMPLE_PINHOLE cameras)
 and images/.  <out_dir>/point_cloud/iteration_N/point_cloud.ply is where `Renderer` and `GaussianModel.load_ply` look.
 --synthetic trains against renders of `synthetic.textured_sphere` instead (no dataset needed).  Prints the wall time per
 iteration and its split into render forward, loss, backward and optimiser + densification (stream time between events).
 --loss fused computes L1 + D-SSIM and its gradient with the HIP kernels (training.fused_loss) instead of torch ops.
+--optimizer fused takes the Adam step and the densification statistics with the HIP kernels (optim.FusedAdam) instead of
+torch.optim.Adam and boolean-mask indexing; --optimizer sparse_adam steps only the Gaussians the view saw.
 """
 import argparse
 import json
@@ -65,6 +68,8 @@ def main():
     ap.add_argument("--white-background", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--loss", choices=("torch", "fused"), default="torch", help="torch ops (default) or the fused HIP kernels")
+    ap.add_argument("--optimizer", choices=("default", "fused", "sparse_adam"), default="default",
+                    help="torch.optim.Adam (default), the fused HIP step, or the fused step on the visible rows only")
     ap.add_argument("--synthetic-size", type=int, nargs=4, default=[20000, 4000, 800, 600], metavar=("P_TRUE", "P_INIT", "W", "H"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -83,7 +88,7 @@ def main():
         out_dir = a.paths[1]
         cameras, images, pcd = load_colmap(a.paths[0], a.resolution_scale, device)
     # schedules written in iterations scale with a short run the way the reference's defaults sit in 30 000
-    opt = training.OptimizationParams(iterations=a.iterations, position_lr_max_steps=a.iterations)
+    opt = training.OptimizationParams(iterations=a.iterations, position_lr_max_steps=a.iterations, optimizer_type=a.optimizer)
     if a.iterations < 30_000:
         f = a.iterations / 30_000
         opt.densify_from_iter = max(1, int(500 * f))
@@ -115,7 +120,7 @@ def main():
     split = {name: statistics.fmean(v) for name, v in timing.items()}
     print(json.dumps({
         "ply": ply, "views": len(cameras), "width": cameras[0].image_width, "height": cameras[0].image_height,
-        "iterations": a.iterations, "loss_path": a.loss, "gaussians_start": P0, "gaussians_end": int(g.get_xyz.shape[0]),
+        "iterations": a.iterations, "loss_path": a.loss, "optimizer": a.optimizer, "gaussians_start": P0, "gaussians_end": int(g.get_xyz.shape[0]),
         "loss_first_tenth": statistics.fmean(losses[:k]), "loss_last_tenth": statistics.fmean(losses[-k:]),
         "wall_ms_per_iteration": 1e3 * wall / max(1, a.iterations),
         "stream_ms_per_iteration": {"render_forward": split["render"], "loss": split["loss"], "backward": split["backward"],
