@@ -1,0 +1,272 @@
+"""Geometric evaluation of a mesh against a ground-truth point set, on the GPU.
+
+The reference judges its meshes by geometry: DTU accuracy / completeness (evaluation/DTU/eval_code/eval.py), MobileBrick
+accuracy / recall / F1 / Chamfer (evaluation/MobileBrick/eval_code/evaluate.py) and the TNT F-score.  The core of all three
+is the nearest neighbour of millions of points in another set of millions, which they run on host cores through KD and ball
+trees, and (DTU) a surface sampler run in a multiprocessing pool.  Here both are HIP kernels: ``gs2m_nn_dist2`` (exact,
+ties to the smallest index) and ``gs2m_mesh_sample_count`` / ``_emit`` (bit-identical to the reference's sampler);
+include/gs2mesh_amd.h states their arithmetic.  Everything around them is torch on the same device.
+
+Precision.  The sampler and every filter work in f64 like the reference.  The nearest-neighbour kernel works in f32, so the
+coordinates reach it as ``f32(p - origin)`` with the subtraction in f64; ``origin`` defaults to the midpoint of the ground
+truth's bounding box, ``(gt.min(0) + gt.max(0)) / 2``, which keeps the f32 coordinates of a scene of extent E below E / 2
+(spacing E * 2^-25: 2e-5 mm on a 600 mm DTU scan).  Distances are ``sqrt`` in f64 of the f32 squared distance, means are f64
+sums on the device.
+
+Outside this module, as in DESIGN.md: DTU's ``cull_scan`` (needs the dataset's per-view masks), TNT's registration and
+cropping, MobileBrick's visibility volume and ICP, Poisson-disk sampling.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .rasterizer import _ptr, _stream_of, morton_order
+
+MORTON_MIN_N = 1024     # below this one super-box holds every group: the sort buys nothing
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _device(device):
+    if device is not None:
+        return int(device)
+    torch = _torch()
+    return torch.cuda.current_device() if torch.cuda.is_available() else 0
+
+
+def _tensor(a, dtype, device=None):
+    """anything array-like -> contiguous tensor of ``dtype`` where the memory policy keeps its buffers"""
+    torch = _torch()
+    if not isinstance(a, torch.Tensor):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    if a.is_cuda:
+        return a.to(dtype).contiguous()
+    return _lib.MEMORY.upload(a, dtype, _device(device))
+
+
+def _points(a, dtype, name, device=None):
+    t = _tensor(a, dtype, device)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must be [N,3], got {tuple(t.shape)}")
+    return t
+
+
+# ---- the two kernels ---------------------------------------------------------------------------------------------------
+
+def nearest_neighbors(queries, refs, sort=True, lib=None, want_index=True):
+    """``gs2m_nn_dist2``: for every row of ``queries`` [Q,3] f32 the squared distance to, and the index of, its nearest row
+    of ``refs`` [R,3] f32 -> (d2 [Q] f32, idx [Q] int32), on the tensors' device, asynchronous on the current stream.
+    Exact in the f32 arithmetic of include/gs2mesh_amd.h; exact ties go to the smallest index; R = 0 gives (+inf, -1).
+    ``sort``: walk each side of at least 1024 points along its Morton curve (``rasterizer.morton_order``); it changes the
+    time, never a bit of the result.  ``want_index=False`` returns (d2, None)."""
+    torch = _torch()
+    lib = lib or _lib.get()
+    q = _points(queries, torch.float32, "queries")
+    r = _points(refs, torch.float32, "refs", q.device.index if q.is_cuda else None)
+    if r.device != q.device:
+        raise ValueError(f"nearest_neighbors: queries on {q.device}, refs on {r.device}")
+    Q, R = int(q.shape[0]), int(r.shape[0])
+    d2 = torch.empty((Q,), dtype=torch.float32, device=q.device)
+    idx = torch.empty((Q,), dtype=torch.int32, device=q.device) if want_index else None
+    if Q == 0:
+        return d2, idx
+    qo = morton_order(q) if sort and Q >= MORTON_MIN_N else None
+    ro = morton_order(r) if sort and R >= MORTON_MIN_N else None
+    need = int(lib.gs2m_nn_scratch_bytes(Q, R))
+    scratch = torch.empty(((need + 15) // 16 * 2,), dtype=torch.int64, device=q.device) if need else None
+    _lib.check(lib.gs2m_nn_dist2(Q, _ptr(q, torch.float32, "queries"), _ptr(qo, torch.int32, "query_order"), R,
+                                 _ptr(r, torch.float32, "refs"), _ptr(ro, torch.int32, "ref_order"), _ptr(scratch),
+                                 0 if scratch is None else scratch.shape[0] * 8, _ptr(d2), _ptr(idx), _stream_of(q, None)), lib)
+    return d2, idx
+
+
+def sample_mesh(mesh_or_arrays, density, lib=None, device=None):
+    """The DTU evaluation's mesh -> point set (eval.py:48-71) -> [V + S, 3] f64 on the device: the vertices, then for every
+    triangle of non-zero area, in triangle order, its barycentric grid at ``density`` (``gs2m_mesh_sample_count`` /
+    ``_emit``, bit-identical to the reference's ``sample_single_tri``).  ``mesh_or_arrays``: a ``mesh.TriangleMesh`` or
+    ``(vertices [V,3], triangles [T,3])``.  Raises if a triangle names a vertex outside the mesh, if one triangle would take
+    more than 1 048 576 grid nodes or the mesh more than 2^31 - 1 samples (``density`` far too small for the mesh's units)."""
+    torch = _torch()
+    lib = lib or _lib.get()
+    if hasattr(mesh_or_arrays, "vertices"):
+        verts, tris = mesh_or_arrays.vertices, mesh_or_arrays.triangles
+    else:
+        verts, tris = mesh_or_arrays
+    v = _tensor(verts, torch.float64, device).reshape(-1, 3)
+    t = _tensor(tris, torch.int32, v.device.index if v.is_cuda else device).reshape(-1, 3)
+    V, T = int(v.shape[0]), int(t.shape[0])
+    counts = torch.empty((T,), dtype=torch.int32, device=v.device)
+    offsets = torch.empty((T,), dtype=torch.int32, device=v.device)
+    state = torch.empty((T // 4096 + 4,), dtype=torch.int64, device=v.device)
+    total, status = C.c_int64(0), C.c_uint32(0)
+    stream = _stream_of(v, None)
+    _lib.check(lib.gs2m_mesh_sample_count(V, _ptr(v), T, _ptr(t), float(density), _ptr(counts), _ptr(offsets), _ptr(state),
+                                          state.shape[0] * 8, stream, C.byref(total), C.byref(status)), lib)
+    if status.value & _lib.MESH_SAMPLE_INDEX:
+        raise ValueError(f"sample_mesh: a triangle names a vertex outside 0..{V - 1}")
+    if status.value & _lib.MESH_SAMPLE_CAP:
+        raise ValueError(f"sample_mesh: a triangle would take more than 1048576 grid nodes at density {density}")
+    if status.value & _lib.MESH_SAMPLE_TOTAL:
+        raise ValueError(f"sample_mesh: {total.value} samples at density {density}, more than 2^31 - 1")
+    points = torch.empty((V + total.value, 3), dtype=torch.float64, device=v.device)
+    _lib.check(lib.gs2m_mesh_sample_emit(V, _ptr(v), T, _ptr(t), float(density), _ptr(counts), _ptr(offsets), total.value,
+                                         _ptr(points), stream), lib)
+    return points
+
+
+# ---- torch around them -------------------------------------------------------------------------------------------------
+
+def thin_points(points, cell, return_index=False):
+    """One point per occupied cubic cell of edge ``cell`` (cell = floor(p / cell) per axis, f64): the point with the lowest
+    index wins, and the survivors keep their order.  Torch ops, no kernel.
+
+    This is the deliberate substitute for the reference's thinning (eval.py:79-94), which shuffles the points with an unseeded
+    generator and then keeps them greedily -- a point survives unless an earlier survivor lies within ``density`` -- in one
+    sequential Python pass: its result differs from run to run of the reference itself, so there is nothing to reproduce.
+    Both leave a set whose points are about ``cell`` apart and that covers the input to within ``cell * sqrt(3)``."""
+    torch = _torch()
+    p = _points(points, torch.float64, "points")
+    n = int(p.shape[0])
+    if n == 0:
+        keep = torch.zeros((0,), dtype=torch.int64, device=p.device)
+        return (p, keep) if return_index else p
+    if not cell > 0:
+        raise ValueError(f"thin_points: cell = {cell}")
+    ijk = torch.floor(p / float(cell)).to(torch.int64)
+    ijk = ijk - ijk.amin(dim=0)
+    dims = (ijk.amax(dim=0) + 1).tolist()
+    if dims[0] * dims[1] * dims[2] < 2 ** 62:
+        key = (ijk[:, 0] * dims[1] + ijk[:, 1]) * dims[2] + ijk[:, 2]
+        _, inv = torch.unique(key, return_inverse=True)
+    else:
+        _, inv = torch.unique(ijk, dim=0, return_inverse=True)
+    first = torch.full((int(inv.max().item()) + 1,), n, dtype=torch.int64, device=p.device)
+    first.scatter_reduce_(0, inv, torch.arange(n, dtype=torch.int64, device=p.device), reduce="amin")
+    keep = torch.sort(first).values
+    return (p[keep], keep) if return_index else p[keep]
+
+
+def dtu_observation_filter(points, obs_mask, bb, res, patch=60):
+    """eval.py:102-110 restated -> (inbound, observed), two bool masks over ``points`` [N,3] f64:
+    ``inbound``  = all(p >= f32(BB[0]) - patch) and all(p < f32(BB[1]) + 2 * patch), the bounds in f32 as the reference's;
+    ``observed`` = inbound, and g = round_half_even((p - f32(BB[0])) / Res) lies inside ``obs_mask`` and obs_mask[g] is set.
+    The reference measures data -> GT on the observed points and GT -> data against the inbound ones."""
+    torch = _torch()
+    p = _points(points, torch.float64, "points")
+    dev = p.device
+    bb32 = torch.from_numpy(np.ascontiguousarray(np.asarray(bb, np.float64).reshape(2, 3).astype(np.float32))).to(dev)
+    lo = (bb32[0] - float(patch)).to(torch.float64)
+    hi = (bb32[1] + float(patch) * 2).to(torch.float64)
+    inbound = ((p >= lo) & (p < hi)).all(dim=1)
+    mask = torch.from_numpy(np.ascontiguousarray(np.asarray(obs_mask) != 0)).to(dev)
+    if mask.ndim != 3:
+        raise ValueError(f"obs_mask must be 3-D, got {tuple(mask.shape)}")
+    r = float(np.asarray(res, np.float64).reshape(-1)[0])
+    g = torch.round((p - bb32[0].to(torch.float64)) / r)
+    shape = torch.tensor(list(mask.shape), dtype=torch.float64, device=dev)
+    inside = inbound & ((g >= 0) & (g < shape)).all(dim=1)
+    gi = torch.where(inside[:, None], g, torch.zeros_like(g)).to(torch.int64)
+    observed = inside & mask[gi[:, 0], gi[:, 1], gi[:, 2]]
+    return inbound, observed
+
+
+def above_plane(points, plane):
+    """eval.py:128-130 restated -> bool mask: ((P0 * x + P1 * y) + P2 * z) + P3 > 0 in f64."""
+    torch = _torch()
+    p = _points(points, torch.float64, "points")
+    P = [float(x) for x in np.asarray(plane, np.float64).reshape(4)]
+    return ((P[0] * p[:, 0] + P[1] * p[:, 1]) + P[2] * p[:, 2]) + P[3] > 0
+
+
+def _origin(gt, origin):
+    torch = _torch()
+    if origin is not None:
+        return torch.as_tensor(np.asarray(origin, np.float64).reshape(3)).to(gt.device)
+    if gt.shape[0] == 0:
+        return torch.zeros(3, dtype=torch.float64, device=gt.device)
+    return (gt.amin(dim=0) + gt.amax(dim=0)) / 2
+
+
+def _distances(queries, refs, origin, sort, lib):
+    """[Q] f64: sqrt in f64 of the f32 squared distance between f32(queries - origin) and f32(refs - origin)"""
+    torch = _torch()
+    d2, _ = nearest_neighbors((queries - origin).to(torch.float32), (refs - origin).to(torch.float32), sort=sort, lib=lib,
+                              want_index=False)
+    return torch.sqrt(d2.to(torch.float64))
+
+
+def _mean(x):
+    return float(x.sum(dtype=_torch().float64).item()) / int(x.shape[0]) if int(x.shape[0]) else float("nan")
+
+
+def dtu_metrics(pred_points, gt_points, max_dist=20, pred_refs=None, gt_queries=None, origin=None, sort=True, lib=None):
+    """eval.py:117-134, 157 -> {mean_d2s, mean_s2d, overall}: ``mean_d2s`` the mean distance from ``pred_points`` to
+    ``gt_points``, ``mean_s2d`` from ``gt_queries`` (default: ``gt_points``; the reference: the part above the ground
+    plane) to ``pred_refs`` (default: ``pred_points``; the reference: the inbound points before the observation mask), each
+    over the distances < ``max_dist`` only (a distance equal to it is left out; none left gives NaN, as numpy's mean of
+    nothing), ``overall`` their mean."""
+    torch = _torch()
+    pred = _points(pred_points, torch.float64, "pred_points")
+    dev = pred.device.index if pred.is_cuda else None
+    gt = _points(gt_points, torch.float64, "gt_points", dev)
+    refs = pred if pred_refs is None else _points(pred_refs, torch.float64, "pred_refs", dev)
+    gq = gt if gt_queries is None else _points(gt_queries, torch.float64, "gt_queries", dev)
+    o = _origin(gt, origin)
+    d2s = _distances(pred, gt, o, sort, lib)
+    s2d = _distances(gq, refs, o, sort, lib)
+    mean_d2s = _mean(d2s[d2s < max_dist])
+    mean_s2d = _mean(s2d[s2d < max_dist])
+    return {"mean_d2s": mean_d2s, "mean_s2d": mean_s2d, "overall": (mean_d2s + mean_s2d) / 2}
+
+
+def fscore_metrics(pred_points, gt_points, thresholds, origin=None, sort=True, lib=None):
+    """MobileBrick's ``evaluate`` (evaluate.py:46-63) for any number of thresholds -> {pred_gt, gt_pred, chamfer,
+    thresholds: {str(t): {accuracy, recall, F1}}}: ``pred_gt`` / ``gt_pred`` the mean nearest-neighbour distances,
+    ``chamfer`` their sum, ``accuracy`` / ``recall`` the shares of those distances < t, ``F1`` their harmonic mean --
+    reported as 0 where both are 0 (the reference divides 0 by 0 there)."""
+    torch = _torch()
+    pred = _points(pred_points, torch.float64, "pred_points")
+    gt = _points(gt_points, torch.float64, "gt_points", pred.device.index if pred.is_cuda else None)
+    o = _origin(gt, origin)
+    d_pg = _distances(pred, gt, o, sort, lib)
+    d_gp = _distances(gt, pred, o, sort, lib)
+    out = {"pred_gt": _mean(d_pg), "gt_pred": _mean(d_gp)}
+    out["chamfer"] = out["pred_gt"] + out["gt_pred"]
+    out["thresholds"] = {}
+    for t in thresholds:
+        acc = float((d_pg < t).sum().item()) / int(d_pg.shape[0]) if int(d_pg.shape[0]) else float("nan")
+        rec = float((d_gp < t).sum().item()) / int(d_gp.shape[0]) if int(d_gp.shape[0]) else float("nan")
+        f1 = 0.0 if acc + rec == 0 else 2 * acc * rec / (acc + rec)
+        out["thresholds"][str(t)] = {"accuracy": acc, "recall": rec, "F1": f1}
+    return out
+
+
+def evaluate_mesh(mesh, gt_points, density=0.2, max_dist=20, thresholds=(), obs_mask=None, bb=None, res=None, plane=None,
+                  patch=60, origin=None, sort=True, lib=None, device=None):
+    """The DTU evaluation of a mesh (eval.py:43-134), from arrays instead of the dataset's directory: sample at ``density``,
+    thin to one point per cell of edge ``density`` (``thin_points``), then -- when ``obs_mask`` / ``bb`` / ``res`` are given --
+    keep the inbound and observed points, and -- when ``plane`` is given -- the ground truth above it; ``dtu_metrics`` of what
+    is left.  With ``thresholds`` the MobileBrick figures of the same two sets (``fscore_metrics``) come under "fscore".
+    -> {mean_d2s, mean_s2d, overall, n_sampled, n_thinned, n_observed, n_gt[, fscore]}."""
+    torch = _torch()
+    pts = sample_mesh(mesh, density, lib=lib, device=device)
+    dev = pts.device.index if pts.is_cuda else None
+    gt = _points(gt_points, torch.float64, "gt_points", dev)
+    down = thin_points(pts, density)
+    data_in, data_obs = down, down
+    if obs_mask is not None:
+        inbound, observed = dtu_observation_filter(down, obs_mask, bb, res, patch)
+        data_in, data_obs = down[inbound], down[observed]
+    gt_q = gt if plane is None else gt[above_plane(gt, plane)]
+    o = _origin(gt, origin)
+    out = dtu_metrics(data_obs, gt, max_dist, pred_refs=data_in, gt_queries=gt_q, origin=o.cpu().numpy(), sort=sort, lib=lib)
+    out.update(n_sampled=int(pts.shape[0]), n_thinned=int(down.shape[0]), n_observed=int(data_obs.shape[0]), n_gt=int(gt_q.shape[0]))
+    if len(thresholds):
+        out["fscore"] = fscore_metrics(data_obs, gt_q, thresholds, origin=o.cpu().numpy(), sort=sort, lib=lib)
+    return out

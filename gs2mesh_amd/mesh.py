@@ -234,3 +234,54 @@ def read_triangle_mesh(path) -> TriangleMesh:
     if "red" in names:
         m.vertex_colors = np.stack([v["red"], v["green"], v["blue"]], 1) / 255.0
     return m
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_point_cloud(path) -> np.ndarray:
+    """The vertex positions of any PLY whose vertex element comes first -> [N,3] f64: ``binary_little_endian`` or ``ascii``,
+    ``x y z`` as float or double among any other scalar vertex properties; later elements (faces) are ignored.  For
+    ground-truth point sets and for meshes other programs wrote; ``read_triangle_mesh`` reads this package's own files."""
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, props, nv, cur, first = None, [], 0, None, None
+        while True:
+            line = fh.readline()
+            if not line:
+                raise ValueError(f"{path}: no end_header")
+            tok = line.decode("ascii", errors="replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                cur = tok[1]
+                first = first or cur
+                if cur == "vertex":
+                    nv = int(tok[2])
+            elif tok[0] == "property" and cur == "vertex":
+                if tok[1] == "list" or tok[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: vertex property {' '.join(tok[1:])} is not a scalar")
+                props.append((tok[-1], _PLY_TYPES[tok[1]]))
+            elif tok[0] == "end_header":
+                break
+        names = [p[0] for p in props]
+        if first != "vertex" or not all(a in names for a in "xyz"):
+            raise ValueError(f"{path}: the first element must be `vertex` with x, y and z")
+        if fmt == "binary_little_endian":
+            dt = np.dtype([(n, "<" + t) for n, t in props])
+            raw = fh.read(nv * dt.itemsize)
+            if len(raw) != nv * dt.itemsize:
+                raise ValueError(f"{path}: {nv} vertices declared, the file ends before")
+            v = np.frombuffer(raw, dtype=dt, count=nv)
+            return np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float64)
+        if fmt == "ascii":
+            rows = np.loadtxt(fh, dtype=np.float64, max_rows=nv, ndmin=2) if nv else np.zeros((0, len(props)))
+            if rows.shape != (nv, len(props)):
+                raise ValueError(f"{path}: {nv} vertices of {len(props)} properties declared, found {rows.shape}")
+            return np.ascontiguousarray(rows[:, [names.index(a) for a in "xyz"]])
+        raise ValueError(f"{path}: format {fmt} (binary_little_endian or ascii)")

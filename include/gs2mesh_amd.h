@@ -641,6 +641,73 @@ int gs2m_knn_mean_dist2(int P, const float* points, const int32_t* order, void* 
                         gs2m_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* mesh evaluation: cross-set nearest neighbour and the DTU surface sampler             */
+/* ------------------------------------------------------------------------------------ */
+
+/*
+ * For every query i of queries[Q][3] its nearest neighbour among refs[R][3]: the hot path of the reference's geometric
+ * metrics (evaluation/DTU/eval_code/eval.py:119-134, evaluation/MobileBrick/eval_code/evaluate.py:46-63), which run it on
+ * the host through KD and ball trees.  Exact, defined bit for bit:
+ *   - d(i, j) = (dx * dx + dy * dy) + dz * dz in f32, every operation rounded on its own (no FMA);
+ *   - selection starts from (+inf, none); candidate j replaces the best when d < best, or when d == best and j is the smaller
+ *     index in the caller's numbering ("none" is larger than every index).  A NaN d never replaces.  So exact ties go to the
+ *     smallest index and the result is a function of the two point sets alone: not of the orders, not of the launch shape;
+ *   - out_d2[i] = the resulting d, out_idx[i] = the resulting j, -1 if none.  R = 0 gives (+inf, -1), so does a query with
+ *     a NaN coordinate; a reference with a NaN coordinate is never returned; references farther than f32 can square give
+ *     d = +inf with a valid index.
+ *   queries, refs           [Q][3], [R][3] f32 device
+ *   query_order, ref_order  NULL, or [Q] / [R] int32 device: permutations, position -> index, in which the sets are walked.
+ *                           They affect the speed only (sort both along the same space-filling curve: whole groups of far
+ *                           references are then culled by their boxes, and the walk starts next to the answer), never the
+ *                           result.  An entry outside its range is replaced by its position, so no access leaves the arrays.
+ *   scratch, scratch_bytes  device, 16-byte aligned, at least gs2m_nn_scratch_bytes(Q, R) (0 when R = 0: may be NULL);
+ *                           nothing in it outlives the call
+ *   out_d2                  [Q] f32 device, indexed like `queries`
+ *   out_idx                 NULL, or [Q] int32 device
+ * Q = 0 does nothing and returns 0.  Stateless, asynchronous on `stream`, no allocation, no atomics, the same bits on every
+ * run; bad arguments return 1 with gs2m_last_error().
+ */
+int64_t gs2m_nn_scratch_bytes(int Q, int R);
+int gs2m_nn_dist2(int Q, const float* queries, const int32_t* query_order, int R, const float* refs, const int32_t* ref_order,
+                  void* scratch, int64_t scratch_bytes, float* out_d2, int32_t* out_idx, gs2m_stream stream);
+
+/*
+ * The DTU evaluation's mesh -> point set (evaluation/DTU/eval_code/eval.py:10-19, 54-71): all vertices, then for every
+ * triangle (v0, v1, v2) of non-zero area a regular barycentric grid.  In f64, every operation rounded on its own:
+ *   a = v1 - v0, b = v2 - v0;  L1 = sqrt((ax*ax + ay*ay) + az*az), L2 likewise from b;
+ *   c = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx),  A = sqrt((cx*cx + cy*cy) + cz*cz);  not A > 0: no samples;
+ *   thr = density * sqrt(L1 * L2 / A),  N1 = floor(L1 / thr),  N2 = floor(L2 / thr);
+ *   for i = 0 .. N1 (major), j = 0 .. N2 (minor):  c0 = (i + 0.5) / max(N1, 1e-7),  c1 = (j + 0.5) / max(N2, 1e-7),
+ *   if c0 + c1 < 1: the next sample is (a * c0 + b * c1) + v0, per component.
+ * So N1 = 0 or N2 = 0 gives no sample.  Bit-identical to the reference's sample_single_tri on the grids it was run on
+ * (tests/golden/dtu_sample_tri.npz).
+ *
+ * gs2m_mesh_sample_count writes counts[t] and their exclusive prefix sums offsets[t], synchronises `stream` once and returns
+ * the number of samples in *total and these bits in *status:
+ *   GS2M_MESH_SAMPLE_CAP     a triangle with (N1 + 1) * (N2 + 1) > 1 048 576 was not sampled (count 0)
+ *   GS2M_MESH_SAMPLE_TOTAL   *total > 2^31 - 1: offsets[] wrapped, gs2m_mesh_sample_emit refuses such a total
+ *   GS2M_MESH_SAMPLE_INDEX   a triangle names a vertex outside [0, n_vertices); it is never dereferenced (count 0)
+ * gs2m_mesh_sample_emit, with the same mesh and density, writes points[n_vertices + total][3]: the vertices, then the
+ * samples in triangle order.  No row at or past n_vertices + total is written whatever counts and offsets hold.
+ *   vertices                [n_vertices][3] f64 device;  triangles [n_triangles][3] int32 device
+ *   counts, offsets         [n_triangles] u32 device
+ *   state, state_bytes      device, 8-byte aligned, at least GS2M_MESH_SAMPLE_STATE_BYTES(n_triangles); nothing in it
+ *                           outlives the call
+ * n_triangles = 0 gives total 0 and emit copies the vertices.  Stateless, no allocation, emit is asynchronous on `stream`;
+ * bad arguments return 1 with gs2m_last_error().
+ */
+#define GS2M_MESH_SAMPLE_CAP 1u
+#define GS2M_MESH_SAMPLE_TOTAL 2u
+#define GS2M_MESH_SAMPLE_INDEX 4u
+#define GS2M_MESH_SAMPLE_STATE_BYTES(n_triangles) (16 + 4 * ((int64_t)(n_triangles) / 4096 + 2))
+int gs2m_mesh_sample_count(int64_t n_vertices, const double* vertices, int64_t n_triangles, const int32_t* triangles,
+                           double density, uint32_t* counts, uint32_t* offsets, void* state, int64_t state_bytes,
+                           gs2m_stream stream, int64_t* total, uint32_t* status);
+int gs2m_mesh_sample_emit(int64_t n_vertices, const double* vertices, int64_t n_triangles, const int32_t* triangles,
+                          double density, const uint32_t* counts, const uint32_t* offsets, int64_t total, double* points,
+                          gs2m_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* photometric loss of 3DGS training (L1 + D-SSIM, GS/utils/loss_utils.py, train.py:89-90) */
 /* ------------------------------------------------------------------------------------ */
 
