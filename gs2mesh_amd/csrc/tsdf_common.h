@@ -9,9 +9,12 @@
 //     mean = sum / weight);
 //   * SoA, block-major; inside a block the 4096 voxels are stored as 64 micro-blocks of 4x4x4:
 //     voxel (x,y,z) at ((z>>2)*16 + (x>>2)*4 + (y>>2))*64 + (z&3)*16 + (x&3)*4 + (y&3).  A wave owns
-//     one micro-block per step: its 64 state words are 256 contiguous bytes (one coalesced access per
-//     array) AND its 64 voxel centres project into a ~14x14-pixel patch, so the depth / colour gathers
-//     touch ~4x fewer cache lines than a 4x16 slice of a z-plane would.
+//     one micro-block per memory instruction, lane = (z&3)*16 + (x&3)*4 + (y&3): its 64 state words are
+//     256 contiguous bytes (one coalesced access per array) AND its 64 voxel centres project into a
+//     ~14x14-pixel patch, so a depth / colour gather touches less than half the cache lines that a 4x16
+//     slice of a z-plane would (tools/tsdf_gather_lines.py counts them).  Both sweeps gather that way:
+//     k_tsdf_integrate walks a block's micro-blocks four at a time, k_tsdf_integrate_batch gives a wave
+//     the 4 micro-blocks stacked along z and keeps their state in registers over the frames of a batch.
 #pragma once
 #include "platform.h"
 

@@ -411,33 +411,45 @@ k_tsdf_integrate(TsdfVolume V, TsdfFrame f, const float* __restrict__ depth, con
 }
 
 // k_tsdf_integrate_batch: the frames of a batch in ONE sweep over the touched blocks, voxel-stationary (SURVEY.md 7,
-// step 6 iii).  A 256-thread workgroup owns a z-quarter zq of a block; thread (x, y) keeps the state of the 4 voxels
-// (x, y, 4 zq .. 4 zq + 3) in registers (20 words), walks the frames that touched the block IN FRAME ORDER (bit f of the
+// step 6 iii).  A 256-thread workgroup owns an x-quarter xq of a block, wave w its micro-column (xq, yq = w): the 4 micro-blocks
+// stacked along z.  Lane (lz, lx, ly) -- laid out as in k_tsdf_integrate -- keeps the state of its position in each of them, the 4
+// voxels (4 xq + lx, 4 w + ly, 4 j + lz), j = 0 .. 3, in registers (20 words).  So gather instruction j of a wave covers exactly
+// micro-block (j, xq, w), the compact pixel patch the storage order was chosen for (tsdf_common.h), and a state load or store
+// of it is 256 contiguous bytes per array.  The thread walks the frames that touched the block IN FRAME ORDER (bit f of the
 // block's frame mask; Open3D integrates a block for a frame only if that frame's points touch it) and applies exactly the
-// per-frame update (same fp32 sequence, same incremental z chain: a thread replays the 4 zq steps below its run once per
-// frame, then steps along it) -- results are bit-identical to calling k_tsdf_integrate frame by frame.  Compared with the
-// per-frame kernel: the voxel state is read and written once per batch instead of once per frame (40 B x updated voxels
-// x frames -> 20 B x voxels of touched blocks), 4.5 instead of ~22 replayed additions per voxel and frame, the distance
-// multiplier (a correctly rounded sqrt) only where a depth sample exists, frame uniforms by scalar loads.
-// One 256-thread workgroup per (block, z-quarter) (round 3; the round-2 form, one 1024-thread workgroup per block at 94 VGPRs =
-// 4 waves per SIMD, was removed in round 4): 88 VGPRs (then) admit 5 such workgroups per CU, the work items are four times finer for
-// the dynamic hand-out, zq (and with it the replay loop of the z chain) is wave-uniform, and the block's frame mask is cleared
-// by k_tsdf_clear_fmask afterwards (the four quarters of a block run on different workgroups).  C2: 39.2 -> 32.7 us per frame
-// in sweeps of 10, 36.9 -> 29.7 in sweeps of 24; forcing 6 / 7 waves per SIMD (80 / 72 VGPRs, spills) gains nothing (32.9 /
-// 35.7).  Same arithmetic per voxel: bit-identical.
-// Round 4, measured and not kept (profiles/r4_experiments.txt): the frames of a block probed four at a time by the four waves
-// of the workgroup ("frame lanes": LDS exchange + barrier per round, one voxel of state per thread) 30 -> 80 us per frame --
-// the dependent round trips only move from the frame loop to a loop over x-quarters; the colour gathered together with the
-// depth (one round trip per frame instead of two dependent ones, but for every probed voxel) 30.5 -> 35.2: the sweep is bound
-// by the number of gathers and its ~12 M vector instructions per frame, not by exposed latency; 6 waves per SIMD (80 VGPRs,
-// 5 spilled) 30.5 -> 30.5 on C2, 76.6 -> 72.1 on C4 (not worth a second kernel).
+// per-frame update (same fp32 sequence, same incremental z chain: per frame the point of voxel (x, y, 0) is advanced by lz
+// steps to the thread's first voxel, then by 4 steps from each voxel to the next -- 15 steps = 45 additions per thread and frame,
+// as many as the longest replay of the per-frame kernel's lane and in the same order) -- results are bit-identical to calling
+// k_tsdf_integrate frame by frame.  Compared with the per-frame kernel: the voxel state is read and written once per batch
+// instead of once per frame (40 B x updated voxels x frames -> 20 B x voxels of touched blocks), the distance multiplier (a
+// correctly rounded sqrt) only where a depth sample exists, frame uniforms by scalar loads.
+// Four work items per block (round 3; the round-2 form, one 1024-thread workgroup per block at 94 VGPRs = 4 waves per SIMD, was
+// removed in round 4): finer items for the dynamic hand-out, and the block's frame mask is cleared by k_tsdf_clear_fmask
+// afterwards (the four quarters of a block run on different workgroups).
+// The lane mapping (profiles/tsdf_sweep_layout.txt; C2 / C4, us per frame in sweeps of 20, builds interleaved in one process):
+// until this form a workgroup owned a z-quarter and thread (x, y) a run of 4 voxels along z, so one gather covered a 4 x 16
+// slice of a z-plane, 2.2x the cache lines of a micro-block (tools/tsdf_gather_lines.py): 28.4 / 67.2.  The same runs with
+// the wave over 8 x 8 of a z-plane: 25.8 / 63.0.  This mapping: 24.6 / 61.0 at 92 VGPRs.  A pending probe keeps neither the
+// pixel index (v * W + u is formed again from the packed (u, v) for the colour gather; NO_PIXEL marks a voxel that sees no
+// pixel) nor the 4 camera-space depths (one start value, the chain's additions are repeated on it): either one alone leaves
+// the time where it was (84 VGPRs, still 5 waves per SIMD: 24.6 / 61.8, 24.4 / 61.2), both give 74 VGPRs = 6 waves per SIMD
+// without a register cap or a spill: 23.5 / 58.5.  In the benchmark's own stage timing the sweep costs 21.7 us per frame on C2 and
+// 59.7 on C4 (27.8 and 75.5 before); the bytes to HBM are what they were, 59 % of the vector-L1 line accesses are gone.
+// Measured and not kept: the two squares of the distance multiplier from LDS tables over the image's columns and rows (16 KiB
+// per workgroup) 24.2 -> 23.7 on C2 with rounds won and lost alike, 58.9 -> 58.0 on C4, and on the 92-VGPR form 24.7 -> 24.9 /
+// 60.8 -> 61.7: no gain that stands out of the run-to-run spread (0.3 - 0.5 us).  Round 3, forcing 6 / 7 waves per SIMD with a
+// register cap (80 / 72 VGPRs, spills) gained nothing.  Round 4 (profiles/r4_experiments.txt): the frames of a block probed four
+// at a time by the four waves of the workgroup ("frame lanes": LDS exchange + barrier per round, one voxel of state per thread)
+// 30 -> 80 us per frame -- the dependent round trips only move from the frame loop to a loop over x-quarters; the colour gathered
+// together with the depth (one round trip per frame instead of two dependent ones, but for every probed voxel) 30.5 -> 35.2.
 GS2M_KERNEL void __launch_bounds__(256)
 k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) {
     __shared__ float s_p0[16], s_p1[16];
     const int tid = (int)threadIdx.x;
-    const int x = (tid >> 4) & 15, y = tid & 15;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int lz = lane >> 4, lx = (lane >> 2) & 3, ly = lane & 3;
     __shared__ unsigned s_it;
-    const unsigned n_touched = V.counters[1] * 4u;   // work items: (block, z-quarter)
+    const unsigned n_touched = V.counters[1] * 4u;   // work items: (block, x-quarter)
     const TsdfFrame& f0 = frames[0].f;   // volume constants (voxel length, truncation) are the same in every frame
     for (;;) {
         // blocks are handed out dynamically (counters[3], zeroed before the launch): a block costs as many frame passes as
@@ -447,7 +459,7 @@ k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) 
         __syncthreads();
         const unsigned it = s_it;
         if (it >= n_touched) break;
-        const int zq = (int)(it & 3u);
+        const int xq = (int)(it & 3u);
         const unsigned h = V.touched[it >> 2];
         const unsigned long long key = V.hash_keys[h];
         const int slot = V.hash_vals[h];
@@ -455,55 +467,63 @@ k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) 
         if (slot < 0) continue;   // pool overflow (flagged); uniform across the workgroup
         const float p2 = tsdf_block_centres(f0, key, tid, s_p0, s_p1);
         __syncthreads();
-        const float p0 = s_p0[x], p1 = s_p1[y];
+        const float p0 = s_p0[4 * xq + lx], p1 = s_p1[4 * wave + ly];
+        const int vi0 = (xq * 4 + wave) * 64 + lane;   // = GS2M_TSDF_VINDEX(x, y, lz); the thread's voxel j (z = 4 j + lz) sits at vi0 + VS * j
+        constexpr int VS = 16 * 64;                    // one micro-block layer of the block
         float* bt = V.tsdf + (size_t)slot * GS2M_TSDF_VOX;
         float* bw = V.weight + (size_t)slot * GS2M_TSDF_VOX;
         unsigned* bc = V.rgb + (size_t)slot * 3 * GS2M_TSDF_VOX;
-        const int vi0 = GS2M_TSDF_VINDEX(x, y, 4 * zq);   // the run z = 4 zq .. 4 zq + 3 sits at vi0 + 16 j (one micro-block)
         float w[4], t[4];
         unsigned c0[4], c1[4], c2[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            w[j] = bw[vi0 + 16 * j];
-            t[j] = bt[vi0 + 16 * j];
+            w[j] = bw[vi0 + VS * j];
+            t[j] = bt[vi0 + VS * j];
             c0[j] = c1[j] = c2[j] = 0u;
             if (V.has_color) {
-                c0[j] = bc[vi0 + 16 * j];
-                c1[j] = bc[GS2M_TSDF_VOX + vi0 + 16 * j];
-                c2[j] = bc[2 * GS2M_TSDF_VOX + vi0 + 16 * j];
+                c0[j] = bc[vi0 + VS * j];
+                c1[j] = bc[GS2M_TSDF_VOX + vi0 + VS * j];
+                c2[j] = bc[2 * GS2M_TSDF_VOX + vi0 + VS * j];
             }
         }
         // Software pipeline over the frames of the block: the projection of frame n + 1 and its depth gathers are issued
         // before frame n is applied, so a wave always has the next frame's memory round trip in flight (the kernel is bound
         // by gather latency: 63 % of the wave cycles wait at 4 waves per SIMD, PMC).  Frames are still APPLIED in ascending
         // order with the same arithmetic: bit-identical to the frame-by-frame path.
+        // What a probe keeps until it is applied is 9 registers (with 17 the kernel stood at 92 VGPRs = 5 waves per SIMD, now 74 = 6).
         struct Probe {
             int fi;
-            int pix[4];
-            unsigned uv[4];        // u | v << 16 (image sizes <= 65535, checked by the host side)
-            float zc[4], d[4];
+            unsigned uv[4];        // u | v << 16 (image sizes <= 65535, checked by the host side), or NO_PIXEL
+            float zc0;             // camera-space z of the thread's first voxel: apply() repeats the chain's additions on it
+            float d[4];
         };
+        constexpr unsigned NO_PIXEL = 0xffffffffu;   // u, v <= 65534: no pixel packs to this
         auto probe = [&](const int fi, Probe& P) __attribute__((always_inline)) {
             const TsdfBatchFrame& bf = frames[fi];
             const TsdfFrame& f = bf.f;
             const float* __restrict__ depth = bf.depth;
             const unsigned char* __restrict__ mask = bf.mask;
             P.fi = fi;
-            // camera-space centre of voxel (x, y, 0), advanced along z to the start of this thread's run
+            // camera-space centre of voxel (x, y, 0), advanced along z to the thread's first voxel (x, y, lz)
             float pc0, pc1, pc2;
             tsdf_cam_point(f, p0, p1, p2, pc0, pc1, pc2);
-            for (int s = 0; s < 4 * zq; ++s) tsdf_z_step(f, pc0, pc1, pc2);
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                if (s < lz) tsdf_z_step(f, pc0, pc1, pc2);
+            }
+            P.zc0 = pc2;
+            int pix[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 int u = 0, v = 0;
-                P.pix[j] = tsdf_project(f, pc0, pc1, pc2, u, v);
-                P.uv[j] = (unsigned)u | ((unsigned)v << 16);
-                P.zc[j] = pc2;
-                tsdf_z_step(f, pc0, pc1, pc2);
+                pix[j] = tsdf_project(f, pc0, pc1, pc2, u, v);
+                P.uv[j] = pix[j] >= 0 ? ((unsigned)u | ((unsigned)v << 16)) : NO_PIXEL;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) tsdf_z_step(f, pc0, pc1, pc2);   // to the same position in the next micro-block
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j)   // depth gathers, back to back (converted and consumed by apply() one frame later)
-                P.d[j] = P.pix[j] >= 0 ? tsdf_read_depth(f, depth, mask, (size_t)P.pix[j]) : 0.0f;
+                P.d[j] = pix[j] >= 0 ? tsdf_read_depth(f, depth, mask, (size_t)pix[j]) : 0.0f;
         };
         auto apply = [&](Probe& P) __attribute__((always_inline)) {
             const TsdfBatchFrame& bf = frames[P.fi];
@@ -513,21 +533,27 @@ k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) 
             unsigned rgbp[4];
             bool upd[4];
             float tnew[4];
+            float zx = 0.0f, zy = 0.0f, zc = P.zc0;   // the z chain again, of which only z is used
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 upd[j] = false;
                 tnew[j] = 0.0f;
                 rgbp[j] = 0u;
+                const bool seen = P.uv[j] != NO_PIXEL;
+                const float zcj = zc;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) tsdf_z_step(f, zx, zy, zc);
                 // (measured, profiles/tsdf_update_once.txt: leaving the iteration early where pix < 0 instead of these two
                 // guards costs the sweep 3 % -- 28.69 / 28.95 / 29.00 against 27.97 / 28.05 / 27.88 us per frame, C2 in sweeps
                 // of 20, runs interleaved in one session -- same arithmetic, another schedule)
                 float dd = P.d[j];
-                if (P.pix[j] >= 0) dd = tsdf_convert_depth(f, dd);
-                if (P.pix[j] >= 0 && dd > 0.0f) {
+                if (seen) dd = tsdf_convert_depth(f, dd);
+                if (seen && dd > 0.0f) {
                     // the distance multiplier (a correctly rounded sqrt) only here, where a depth sample exists
-                    const float mult = tsdf_distance_multiplier(f, (int)(P.uv[j] & 0xffffu), (int)(P.uv[j] >> 16));
-                    upd[j] = tsdf_decide(f, dd, P.zc[j], mult, tnew[j]);
-                    if (upd[j] && V.has_color) rgbp[j] = tsdf_gather_rgb(color, P.pix[j], last_pix);
+                    const int u = (int)(P.uv[j] & 0xffffu), v = (int)(P.uv[j] >> 16);
+                    const float mult = tsdf_distance_multiplier(f, u, v);
+                    upd[j] = tsdf_decide(f, dd, zcj, mult, tnew[j]);
+                    if (upd[j] && V.has_color) rgbp[j] = tsdf_gather_rgb(color, v * f.W + u, last_pix);
                 }
             }
 #pragma unroll
@@ -560,15 +586,15 @@ k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) 
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            bw[vi0 + 16 * j] = w[j];
-            bt[vi0 + 16 * j] = t[j];
+            bw[vi0 + VS * j] = w[j];
+            bt[vi0 + VS * j] = t[j];
             if (V.has_color) {
-                bc[vi0 + 16 * j] = c0[j];
-                bc[GS2M_TSDF_VOX + vi0 + 16 * j] = c1[j];
-                bc[2 * GS2M_TSDF_VOX + vi0 + 16 * j] = c2[j];
+                bc[vi0 + VS * j] = c0[j];
+                bc[GS2M_TSDF_VOX + vi0 + VS * j] = c1[j];
+                bc[2 * GS2M_TSDF_VOX + vi0 + VS * j] = c2[j];
             }
         }
-        if (tid == 0 && zq == 0) atomicAdd(&V.totals[0], (unsigned long long)gs2m_popc64(fm));   // block updates = sum over frames of touched blocks
+        if (tid == 0 && xq == 0) atomicAdd(&V.totals[0], (unsigned long long)gs2m_popc64(fm));   // block updates = sum over frames of touched blocks
     }
 }
 
