@@ -11,6 +11,11 @@ import ctypes as C
 import numpy as np
 import os
 
+try:  # torch is plumbing for device memory / streams; the emulator tests run without a device
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgs2mesh_amd.so")
 
@@ -150,6 +155,10 @@ def bind(lib: C.CDLL, require_all: bool = True) -> C.CDLL:
 
 
 _LIB = None
+_NP2T = {}              # numpy element type -> torch dtype of a buffer
+if torch is not None:
+    _NP2T = {np.float32: torch.float32, np.float64: torch.float64, np.int32: torch.int32, np.uint32: torch.int32,
+             np.int64: torch.int64, np.uint8: torch.uint8}
 
 
 class DeviceMemory:
@@ -159,7 +168,6 @@ class DeviceMemory:
 
     def ptr(self, x, dtype=None, name="tensor"):
         """Device pointer of a contiguous torch tensor.  None / empty -> NULL."""
-        import torch
         if x is None:
             return None
         if not isinstance(x, torch.Tensor):
@@ -175,26 +183,18 @@ class DeviceMemory:
         return C.c_void_p(x.data_ptr())
 
     def buffer_device(self, device):
-        import torch
         return torch.device(f"cuda:{int(device)}")
 
     def zeros(self, shape, np_dtype, device):
         """zero-filled scratch / result buffer on ``device`` (numpy dtype names the element type)"""
-        import torch
-        tdt = {"float32": torch.float32, "float64": torch.float64, "int32": torch.int32, "uint32": torch.int32,
-               "int64": torch.int64, "uint8": torch.uint8}[np.dtype(np_dtype).name]
-        return torch.zeros(tuple(shape), dtype=tdt, device=self.buffer_device(device))
+        return torch.zeros(tuple(shape), dtype=_NP2T[np.dtype(np_dtype).type], device=self.buffer_device(device))
 
     def empty(self, shape, np_dtype, device):
         """uninitialised buffer on ``device`` for results a kernel writes in full (``zeros`` without the fill)"""
-        import torch
-        tdt = {"float32": torch.float32, "float64": torch.float64, "int32": torch.int32, "uint32": torch.int32,
-               "int64": torch.int64, "uint8": torch.uint8}[np.dtype(np_dtype).name]
-        return torch.empty(tuple(shape), dtype=tdt, device=self.buffer_device(device))
+        return torch.empty(tuple(shape), dtype=_NP2T[np.dtype(np_dtype).type], device=self.buffer_device(device))
 
     def upload(self, a, torch_dtype, device):
         """host array or tensor -> contiguous device tensor of ``torch_dtype``"""
-        import torch
         if isinstance(a, torch.Tensor):
             if a.dtype != torch_dtype:
                 a = a.to(torch_dtype)
@@ -208,11 +208,47 @@ class DeviceMemory:
     def current_stream(self, device):
         """the stream torch is enqueueing on for ``device``: calls of the C ABI that touch buffers torch just created (zero
         fills) or that must follow work the caller queued go on it, not on the NULL stream"""
-        import torch
         return C.c_void_p(torch.cuda.current_stream(self.buffer_device(device)).cuda_stream)
 
 
 MEMORY = DeviceMemory()
+
+
+def _is_torch(x):
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+def _ptr(x, dtype=None, name="tensor"):
+    """Pointer for the C ABI: the device pointer of a contiguous torch tensor on a GPU (``MEMORY``).  None -> NULL."""
+    return MEMORY.ptr(x, dtype, name)
+
+
+def _empty(like, shape, np_dtype):
+    if _is_torch(like):
+        return torch.empty(shape, dtype=_NP2T[np_dtype], device=like.device)
+    return np.empty(shape, np_dtype)
+
+
+def _stream_of(x, stream):
+    if stream is not None:
+        return C.c_void_p(int(stream))
+    if _is_torch(x) and x.is_cuda:
+        return C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    return C.c_void_p(0)
+
+
+SCRATCH = {}    # (owner, "torch" / "numpy", device, stream handle or None) -> grow-only int64 buffer
+
+
+def scratch(owner, like, nbytes, stream=None):
+    """The kept, grow-only scratch of one entry point (``owner``) where ``like`` lives: at least ``nbytes`` bytes as int64 words.
+    One per device, shared by its streams (order the calls on one), or with ``stream`` (a ``_stream_of`` handle) one per stream."""
+    handle = None if stream is None else stream.value or 0
+    key = (owner, "torch", str(like.device), handle) if _is_torch(like) else (owner, "numpy", None, None)
+    buf = SCRATCH.get(key)
+    if buf is None or buf.shape[0] * 8 < nbytes:
+        buf = SCRATCH[key] = _empty(like, ((nbytes + 7) // 8,), np.int64)
+    return buf
 
 
 def get() -> C.CDLL:

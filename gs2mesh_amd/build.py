@@ -27,10 +27,12 @@ SOURCES = [
     ("tsdf_kernels.hip", ["-ffp-contract=off"]),
     ("tsdf_api.hip", []),
     ("stereo_kernels.hip", ["-ffp-contract=off"]),
+    ("points_kernels.hip", ["-ffp-contract=off"]),
+    ("train_kernels.hip", ["-ffp-contract=off"]),
     ("png_encode.hip", []),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", os.path.join(CSRC, "hip"), "-I", CSRC,
-          "-Wall", "-Wno-unused-function"]
+          "-Wall", "-Wno-unused-function", "-DGS2M_SPLIT_UNITS"]    # every unit of SOURCES is compiled on its own
 
 
 def _hipcc():

@@ -1,7 +1,6 @@
 // device_memory.h -- who owns the device memory of the native handles.  Host code only: included by raster_api.hip,
 // tsdf_api.hip and png_encode.hip, and compiled as it is against the CPU emulator's platform.h by the tests.
 //
-//   GS2M_HIPCHK    the error macro of the API files
 //   DeviceBuffer   one hipMalloc allocation, grow-only
 //   PinnedBuffer   one hipHostMalloc allocation
 //   ScratchArena   one DeviceBuffer carved into the temporaries of a call
@@ -17,19 +16,9 @@
 
 #include <vector>
 
+#include "api_check.h"
 #include "platform.h"
 #include "roctx_ranges.h"
-
-void gs2m_set_error(const char* fmt, ...);
-
-#define GS2M_HIPCHK(expr)                                                                     \
-    do {                                                                                      \
-        hipError_t e__ = (expr);                                                              \
-        if (e__ != hipSuccess) {                                                              \
-            gs2m_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
 
 template <typename T>
 class DeviceBuffer {

@@ -3,7 +3,7 @@
 // submodules/simple-knn/simple_knn.cu:131-183; GaussianModel.create_from_pcd turns it into the initial scales).
 //
 // Arithmetic (include/gs2mesh_amd.h states it): d = (dx*dx + dy*dy) + dz*dz in f32 without contraction (this header is
-// compiled into stereo_kernels.hip, built with -ffp-contract=off), the three smallest d over all OTHER points, missing
+// compiled into points_kernels.hip, built with -ffp-contract=off), the three smallest d over all OTHER points, missing
 // ones FLT_MAX, out = ((b0 + b1) + b2) / 3.  The three smallest values of a multiset do not depend on the order in
 // which it is walked, so the result is a function of the point set alone: not of `order`, not of the launch shape.
 //

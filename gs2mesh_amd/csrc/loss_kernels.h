@@ -13,7 +13,7 @@
 // occupancy of 5 and 7 waves per SIMD).
 //
 // Arithmetic (include/gs2mesh_amd.h states it; tests/loss_statement.py restates it in numpy).  This header is compiled into
-// stereo_kernels.hip, built with -ffp-contract=off: every operation below is one f32 operation rounded on its own, divisions
+// train_kernels.hip, built with -ffp-contract=off: every operation below is one f32 operation rounded on its own, divisions
 // are IEEE divisions, and parentheses are the order.  w[0..10] come from the host (double, normalised, cast to f32).
 //   filter    F(q)(r, c) = V(H(q)):  H(q)(r, c) = sum_k w[k] * q(r, c + k - 5),  V(h)(r, c) = sum_k w[k] * h(r + k - 5, c),
 //             each sum  acc = 0; for k = 0 .. 10: acc = acc + w[k] * term_k;  q and H(q) are 0 outside the image

@@ -2,7 +2,7 @@
 // (evaluation/DTU/eval_code/eval.py:10-19, 54-71): all vertices, then for every triangle of non-zero area a regular
 // barycentric grid whose pitch follows the density threshold.  The reference builds the grids with a multiprocessing pool.
 //
-// One lane per triangle, f64, every operation rounded on its own (this header is compiled into stereo_kernels.hip, built
+// One lane per triangle, f64, every operation rounded on its own (this header is compiled into points_kernels.hip, built
 // with -ffp-contract=off; sqrt and the division are IEEE).  include/gs2mesh_amd.h states the arithmetic; tests/
 // mesh_sample_statement.py is its numpy form and is pinned, bit for bit, to points the reference's own function returned.
 // The count pass and the emit pass run the same loop, so they agree on every triangle by construction.

@@ -18,7 +18,7 @@
 //            read nor written, and a lane with nothing visible issues no load of p, g, m or v.
 //
 // Arithmetic (include/gs2mesh_amd.h states it; tests/adam_statement.py restates it in numpy).  This header is compiled into
-// stereo_kernels.hip, built with -ffp-contract=off: every operation is one f32 operation rounded on its own, the division
+// train_kernels.hip, built with -ffp-contract=off: every operation is one f32 operation rounded on its own, the division
 // and the square root are the IEEE ones, subnormals are kept, parentheses are the order.  The six scalars come from the
 // host, computed in double and cast to f32 last (adam_scalars):
 //   ss = f32(lr / (1 - beta1^t)), bs = f32(sqrt(1 - beta2^t)), omb1 = f32(1 - beta1), b2 = f32(beta2), omb2 = f32(1 - beta2)

@@ -31,8 +31,6 @@
 #include "../../include/gs2mesh_amd.h"
 #include "platform.h"
 
-void gs2m_set_error(const char* fmt, ...);
-
 #define PNG_THREADS 256
 #define PNG_WAVES (PNG_THREADS / 64)
 #define PNG_CHUNK 16                          // filtered bytes per lane per round of k_png_encode

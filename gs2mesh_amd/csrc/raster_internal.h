@@ -3,6 +3,7 @@
 // differ (projection: -ffp-contract=off for a literal IEEE sequence; blend: default fast
 // contraction, FMA).
 #pragma once
+#include "api_check.h"
 #include "raster_common.h"
 
 size_t gs2m_scatter_lds_bytes(int nv, int tiles, int threads);
@@ -61,6 +62,3 @@ void gs2m_launch_blend_backward(hipStream_t st, int gx, int gy, const unsigned l
                                 const unsigned* row_offset, float* rows, unsigned long long n_rows);
 void gs2m_launch_gaussian_backward(hipStream_t st, const GaussIn& g, const CamUniform* cams, GeomRecs recs,
                                    const unsigned* row_offset, const float* rows, unsigned long long n_rows, const BwOut& out);
-
-// error plumbing (common_api.hip)
-void gs2m_set_error(const char* fmt, ...);

@@ -1,5 +1,6 @@
 // tsdf_internal.h -- launch wrappers of the TSDF kernels.
 #pragma once
+#include "api_check.h"
 #include "tsdf_common.h"
 
 void gs2m_launch_tsdf_touch(hipStream_t st, const TsdfVolume& V, const TsdfFrame& f, const float* depth,
@@ -43,4 +44,3 @@ void gs2m_launch_mesh_bucket_merge(hipStream_t st, unsigned n, unsigned width, c
                                    const unsigned* src, unsigned* dst);
 void gs2m_launch_mesh_vertex_sum(hipStream_t st, unsigned nv, unsigned nt, const unsigned* off, const unsigned* deg, const unsigned* list,
                                  const double* tn, double* vn);
-void gs2m_set_error(const char* fmt, ...);

@@ -23,7 +23,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .rasterizer import _ptr, _stream_of, morton_order
+from ._lib import _ptr, _stream_of
+from .rasterizer import morton_order
 
 MORTON_MIN_N = 1024     # below this one super-box holds every group: the sort buys nothing
 

@@ -19,7 +19,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from .rasterizer import _is_torch, _ptr, _stream_of
+from ._lib import _is_torch, _ptr, _stream_of
 
 try:
     import torch

@@ -7,6 +7,9 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import _lib
+from ._lib import _ptr, _stream_of
+
 
 def _count(x):
     return int(np.prod(x.shape, dtype=np.int64))
@@ -25,8 +28,6 @@ def adam_step(segments, row_visible=None, lib=None, stream=None):
     number of the step being taken (1 for the first), an int.  ``row_visible``: None, or an int32 buffer of one entry per
     leading row of every tensor: only rows whose entry is > 0 are updated, the others are neither read nor written.
     Asynchronous on the stream; nothing is read on the host."""
-    from . import _lib
-    from .rasterizer import _ptr, _stream_of
     lib = lib or _lib.get()
     n = len(segments)
     table = (_lib.AdamSegment * max(n, 1))()
@@ -60,8 +61,6 @@ def adam_step(segments, row_visible=None, lib=None, stream=None):
 def densify_stats(radii, viewspace_grad, max_radii2D, grad_accum, denom, lib=None, stream=None):
     """``gs2m_densify_stats``, in place: where ``radii`` [P] int32 is > 0, ``max_radii2D`` [P] takes the larger radius,
     ``grad_accum`` [P] (or [P,1]) gains the norm of columns 0 and 1 of ``viewspace_grad`` [P,3], and ``denom`` gains 1."""
-    from . import _lib
-    from .rasterizer import _ptr, _stream_of
     lib = lib or _lib.get()
     P = _count(radii)
     i32 = torch.int32 if isinstance(radii, torch.Tensor) else np.int32
@@ -137,7 +136,6 @@ class FusedAdam(torch.optim.Optimizer):
                 grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 segments.append(dict(param=p.data, grad=grad, exp_avg=state["exp_avg"], exp_avg_sq=state["exp_avg_sq"],
                                      step=t, lr=group["lr"], betas=group["betas"], eps=group["eps"]))
-        from . import _lib
         for k in range(0, len(segments), _lib.ADAM_MAX_SEGMENTS):
             adam_step(segments[k:k + _lib.ADAM_MAX_SEGMENTS], row_visible=visible, lib=self._lib)
         return loss

@@ -13,40 +13,12 @@ import math
 import numpy as np
 
 from . import _lib
+from ._lib import _empty, _is_torch, _ptr, _stream_of  # noqa: F401  (kept reachable as rasterizer._ptr)
 
 try:  # torch is plumbing for device memory / streams; the emulator tests run without a device
     import torch
 except Exception:  # pragma: no cover
     torch = None
-
-
-def _is_torch(x):
-    return torch is not None and isinstance(x, torch.Tensor)
-
-
-def _ptr(x, dtype=None, name="tensor"):
-    """Pointer for the C ABI: the device pointer of a contiguous torch tensor on a GPU (``_lib.MEMORY``).  None -> NULL."""
-    return _lib.MEMORY.ptr(x, dtype, name)
-
-
-_NP2T = {}
-if torch is not None:
-    _NP2T = {np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8, np.uint32: torch.int32,
-             np.int64: torch.int64}
-
-
-def _empty(like, shape, np_dtype):
-    if _is_torch(like):
-        return torch.empty(shape, dtype=_NP2T[np_dtype], device=like.device)
-    return np.empty(shape, np_dtype)
-
-
-def _stream_of(x, stream):
-    if stream is not None:
-        return C.c_void_p(int(stream))
-    if _is_torch(x) and x.is_cuda:
-        return C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    return C.c_void_p(0)
 
 
 def auto_cull_level(P: int) -> int:

@@ -7,18 +7,10 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
-from ..rasterizer import _empty, _is_torch, _ptr, _stream_of, morton_order
+from .._lib import _empty, _is_torch, _ptr, _stream_of
+from ..rasterizer import morton_order
 
 MORTON_MIN_P = 1024     # below this one super-box holds every group: the sort buys nothing
-_SCRATCH = {}           # device -> grow-only scratch buffer
-
-
-def _scratch(like, nbytes):
-    key = str(like.device) if _is_torch(like) else "numpy"
-    buf = _SCRATCH.get(key)
-    if buf is None or buf.shape[0] * 8 < nbytes:
-        buf = _SCRATCH[key] = _empty(like, ((nbytes + 7) // 8,), np.int64)
-    return buf
 
 
 def knn_mean_dist2(points, order=None, lib=None, stream=None):
@@ -35,7 +27,7 @@ def knn_mean_dist2(points, order=None, lib=None, stream=None):
     if P == 0:
         return out
     need = int(lib.gs2m_knn_scratch_bytes(P))
-    scratch = _scratch(points, need)
+    scratch = _lib.scratch("knn", points, need)
     f32 = i32 = None
     if _is_torch(points):
         import torch

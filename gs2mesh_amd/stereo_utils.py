@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .rasterizer import _empty, _ptr, _stream_of
+from ._lib import _empty, _ptr, _stream_of
 
 
 def depth_and_occlusion(disparity_LR, disparity_RL, fx, baseline, occlusion_threshold=3, want_depth=True,
@@ -46,16 +46,6 @@ def get_occlusion_mask(L2R_disparity, R2L_disparity, occlusion_threshold, lib=No
 # ---------------------------------------------------------------------------------------------------------------------
 SGM_P1, SGM_P2 = 10, 120
 SGM_MAX_DISPARITY = 1024
-_SGM_SCRATCH = {}       # (kind, device, stream) -> grow-only scratch buffer of gs2m_stereo_sgm
-
-
-def _sgm_scratch(like, nbytes, stream_handle):
-    torch_like = hasattr(like, "is_cuda")
-    key = ("torch", str(like.device), stream_handle.value or 0) if torch_like else ("numpy", None, 0)
-    buf = _SGM_SCRATCH.get(key)
-    if buf is None or buf.shape[0] * 8 < nbytes:
-        buf = _SGM_SCRATCH[key] = _empty(like, ((nbytes + 7) // 8,), np.int64)
-    return buf
 
 
 def sgm_disparity(left_rgb8, right_rgb8, max_disparity, p1=SGM_P1, p2=SGM_P2, want_rl=True, tap=False, lib=None, stream=None):
@@ -74,7 +64,7 @@ def sgm_disparity(left_rgb8, right_rgb8, max_disparity, p1=SGM_P1, p2=SGM_P2, wa
         raise ValueError(f"sgm_disparity: max_disparity must be a multiple of 64 in [64, {SGM_MAX_DISPARITY}] "
                          f"(got {D}) and the image at most 65535 rows (got {W} x {H})")
     st = _stream_of(left_rgb8, stream)
-    scratch = _sgm_scratch(left_rgb8, need, st)
+    scratch = _lib.scratch("sgm", left_rgb8, need, st)
     disp_lr = _empty(left_rgb8, (H, W), np.float32)
     disp_rl = _empty(left_rgb8, (H, W), np.float32) if want_rl else None
     cost = None

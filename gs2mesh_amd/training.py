@@ -12,6 +12,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import _lib
+from ._lib import _empty, _is_torch, _ptr, _stream_of
+
 
 def l1_loss(network_output, gt):
     """loss_utils.py:17-18"""
@@ -90,20 +93,7 @@ def loss_fn(image, gt, lambda_dssim):
 
 
 # ---- the fused loss: gs2m_photo_loss_forward / _backward (gs2mesh_amd/csrc/loss_kernels.h) -----------------------------------
-_LOSS_SCRATCH = {}      # device -> grow-only scratch buffer
-
-
-def _loss_scratch(like, nbytes):
-    from .rasterizer import _empty, _is_torch
-    key = str(like.device) if _is_torch(like) else "numpy"
-    buf = _LOSS_SCRATCH.get(key)
-    if buf is None or buf.shape[0] * 8 < nbytes:
-        buf = _LOSS_SCRATCH[key] = _empty(like, ((nbytes + 15) // 16 * 2,), np.int64)
-    return buf
-
-
 def _loss_planes(image, gt, what):
-    from .rasterizer import _is_torch
     if tuple(image.shape) != tuple(gt.shape) or image.ndim not in (3, 4):
         raise ValueError(f"{what}: image and target must be [C,H,W] or [B,C,H,W] of one shape, got {tuple(image.shape)} and "
                          f"{tuple(gt.shape)}")
@@ -118,8 +108,6 @@ def photo_loss_forward(image, gt, lambda_dssim, want_partials=True, want_map=Fal
     """``gs2m_photo_loss_forward`` on contiguous f32 device tensors (numpy arrays on the emulator back-end of the tests).
     -> (out [3] = loss, mean |x - y|, mean SSIM; partials [3,*image.shape] or None; the SSIM map or None).  Asynchronous on
     the stream; the scratch is kept per device (shared by every stream of it: order the calls on one) and only grows."""
-    from . import _lib
-    from .rasterizer import _empty, _ptr, _stream_of
     lib = lib or _lib.get()
     planes, H, W = _loss_planes(image, gt, "photo_loss_forward")
     if planes * H * W == 0:
@@ -127,7 +115,7 @@ def photo_loss_forward(image, gt, lambda_dssim, want_partials=True, want_map=Fal
     need = int(lib.gs2m_photo_loss_scratch_bytes(planes, H, W))
     if need < 0:
         raise ValueError(f"photo_loss_forward: unsupported size {tuple(image.shape)}")
-    scratch = _loss_scratch(image, need)
+    scratch = _lib.scratch("photo_loss", image, need)
     out = _empty(image, (3,), np.float32)
     partials = _empty(image, (3,) + tuple(image.shape), np.float32) if want_partials else None
     tap = _empty(image, tuple(image.shape), np.float32) if want_map else None
@@ -140,8 +128,6 @@ def photo_loss_forward(image, gt, lambda_dssim, want_partials=True, want_map=Fal
 def photo_loss_backward(image, gt, partials, lambda_dssim, grad_loss, lib=None, stream=None):
     """``gs2m_photo_loss_backward``: ``grad_loss`` is a one-element f32 buffer on the device (never read on the host).
     -> dL/d image, of ``image``'s shape."""
-    from . import _lib
-    from .rasterizer import _empty, _ptr, _stream_of
     lib = lib or _lib.get()
     planes, H, W = _loss_planes(image, gt, "photo_loss_backward")
     if tuple(partials.shape) != (3,) + tuple(image.shape):
@@ -178,7 +164,6 @@ class _FusedLoss(torch.autograd.Function):
 
 
 def _fused(image, gt, lambda_dssim, which, lib, what):
-    from .rasterizer import _is_torch
     if not _is_torch(image):                # the emulator back-end of the tests: the value alone, no graph
         return photo_loss_forward(np.ascontiguousarray(image), np.ascontiguousarray(gt), lambda_dssim, want_partials=False,
                                   lib=lib)[0][which]
@@ -187,7 +172,6 @@ def _fused(image, gt, lambda_dssim, which, lib, what):
     if gt.requires_grad:
         raise RuntimeError(f"{what}: no gradient is computed for the target; detach it")
     _loss_planes(image, gt, what)
-    from . import _lib
     image = image.contiguous()              # the one copy of a non-contiguous render; autograd carries the gradient back
     _lib.MEMORY.ptr(image.detach(), torch.float32, "image")                 # a CPU tensor is an error, before any work
     need_grad = torch.is_grad_enabled() and image.requires_grad

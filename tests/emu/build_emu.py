@@ -2,14 +2,20 @@
 with g++ against the CPU fiber emulator (tests/emu/platform.h).  TEST INFRASTRUCTURE ONLY."""
 import os
 import subprocess
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "gs2mesh_amd", "csrc")
 OUT = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT, "libgs2mesh_emu.so")
-SRCS = ["raster_project.hip", "raster_bin.hip", "raster_blend.hip", "raster_api.hip", "tsdf_kernels.hip",
-        "tsdf_api.hip", "stereo_kernels.hip"]
+if ROOT not in sys.path:         # run as a script
+    sys.path.append(ROOT)
+from gs2mesh_amd.build import SOURCES  # noqa: E402
+
+# the product's list; its per-file flags are not used: contraction is off throughout.  png_encode.hip is built into a library
+# of its own by tests/test_png_encode.py
+SRCS = [src for src, _ in SOURCES if src != "png_encode.hip"]
 
 
 def build(force=False):
@@ -24,7 +30,7 @@ def build(force=False):
         return LIB
     common = ["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-fopenmp", "-ffp-contract=off", "-fno-fast-math",
               "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-Wno-unused-variable",
-              "-I", HERE, "-I", CSRC]
+              "-DGS2M_SPLIT_UNITS", "-I", HERE, "-I", CSRC]
     objs = []
     procs = []
     for s in SRCS:

@@ -57,9 +57,9 @@ def test_full_size(gpu):
     W, H, focal, D = 1600, 1200, 2900.0, 256                 # nearest point: 2900 * 0.245 / 2.9 = 245 px
     rgb8 = rendered_pair(gpu, 300_000, 0.006, W, H, focal, 0.245)
     lib = _lib.get()
-    stereo_utils._SGM_SCRATCH.clear()
+    _lib.SCRATCH.clear()
     lr, rl = stereo_utils.sgm_disparity(rgb8[0], rgb8[1], D)
-    (scratch,) = stereo_utils._SGM_SCRATCH.values()
+    (scratch,) = _lib.SCRATCH.values()
     assert scratch.numel() * 8 == (lib.gs2m_stereo_sgm_scratch_bytes(W, H, D) + 7) // 8 * 8
     lr2, rl2 = stereo_utils.sgm_disparity(rgb8[0], rgb8[1], D)
     gpu.cuda.synchronize()

@@ -27,7 +27,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from gs2mesh_amd import _lib, evaluation  # noqa: E402
-from gs2mesh_amd.rasterizer import _ptr, morton_order  # noqa: E402
+from gs2mesh_amd._lib import _ptr  # noqa: E402
+from gs2mesh_amd.rasterizer import morton_order  # noqa: E402
 
 
 def shell(n, seed):
