@@ -7,6 +7,13 @@
 // ones FLT_MAX, out = ((b0 + b1) + b2) / 3.  The three smallest values of a multiset do not depend on the order in
 // which it is walked, so the result is a function of the point set alone: not of `order`, not of the launch shape.
 //
+// Input that is not finite: the reference's rule (updateKBest, :132-145).  A candidate counts only if its d is below the
+// current third best, which starts at FLT_MAX; so a d that is NaN or not below FLT_MAX never counts, and the triple is
+// the three smallest counting d, padded with FLT_MAX.  A point with a NaN or infinite coordinate therefore gets +inf
+// ((FLT_MAX + FLT_MAX) + FLT_MAX; not NaN, not an error) and changes no other point's result, and a neighbour so far
+// away that d overflows is a neighbour at "no distance": it stands as FLT_MAX, like a missing one.  How the kernel keeps
+// that rule without a test per candidate is said at k_knn_search.
+//
 // Layout.  Pass 1 gathers the points in `order` into 16-byte records (x, y, z, caller's index) and writes one box per
 // GROUP of KNN_GROUP consecutive records; a second small kernel joins KNN_FAN boxes into a super-box.  Pass 2 gives
 // every wave 64 consecutive records as its queries, one per lane, and walks the super-boxes outwards from its own
@@ -49,11 +56,17 @@ static inline KnnScratch knn_scratch_layout(void* base, int P) {
     return s;
 }
 
-// insert d into the ascending triple: the new k-th value is the median of the old (k-1)-th, k-th and d
+// insert d into the ascending triple: the new k-th value is the median of the old (k-1)-th, k-th and d.  v_med3_f32
+// with a NaN operand returns the minimum of the others; the emulator's form has the same rule, so both back-ends run
+// the same function.  A NaN d would thus turn (b0, b1, b2) into (b0, b0, b1): knn_insert must never see one while
+// the triple holds anything below FLT_MAX (k_knn_search says why it does not).
 #ifdef __HIPCC__
 GS2M_DEVICE float knn_med3(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
 #else
-GS2M_DEVICE float knn_med3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
+GS2M_DEVICE float knn_med3(float a, float b, float c) {
+    if (a != a || b != b || c != c) return fminf(fminf(a, b), c);
+    return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c));
+}
 #endif
 GS2M_DEVICE void knn_insert(float& b0, float& b1, float& b2, float d) {
     b2 = knn_med3(b1, b2, d);
@@ -74,9 +87,10 @@ GS2M_DEVICE float knn_box_dist2(float px, float py, float pz, const float4 mn, c
 }
 
 // Pass 1: one workgroup per group.  An `order` entry outside [0, P) (the caller broke the precondition) is replaced by the
-// position, so nothing is ever read or written out of bounds.
+// position, so nothing is ever read or written out of bounds.  A NaN coordinate never enters a box.  With nan_as_inf
+// (the kNN; gs2m_nn_dist2 keeps the NaN, which its key never selects) it is stored as +inf in the record.
 GS2M_KERNEL void __launch_bounds__(KNN_GROUP)
-k_knn_gather(int P, const float* __restrict__ points, const int* __restrict__ order, float4* __restrict__ rec,
+k_knn_gather(int P, const float* __restrict__ points, const int* __restrict__ order, int nan_as_inf, float4* __restrict__ rec,
              float4* __restrict__ box) {
     __shared__ float red[2 * 3 * (KNN_GROUP / 64)];
     const int t = (int)threadIdx.x, g = (int)blockIdx.x;
@@ -86,10 +100,11 @@ k_knn_gather(int P, const float* __restrict__ points, const int* __restrict__ or
         int id = order ? order[pos] : (int)pos;
         if ((unsigned)id >= (unsigned)P) id = (int)pos;
         const float x = points[3 * (size_t)id], y = points[3 * (size_t)id + 1], z = points[3 * (size_t)id + 2];
-        rec[pos] = make_float4(x, y, z, __int_as_float(id));
-        lo[0] = hi[0] = x;
-        lo[1] = hi[1] = y;
-        lo[2] = hi[2] = z;
+        rec[pos] = make_float4(nan_as_inf && x != x ? INFINITY : x, nan_as_inf && y != y ? INFINITY : y,
+                               nan_as_inf && z != z ? INFINITY : z, __int_as_float(id));
+        if (x == x) lo[0] = hi[0] = x;
+        if (y == y) lo[1] = hi[1] = y;
+        if (z == z) lo[2] = hi[2] = z;
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -134,6 +149,11 @@ k_knn_super(int groups, int supers, const float4* __restrict__ box, float4* __re
 GS2M_DEVICE int knn_outward(int centre, int t) { return (t & 1) ? centre + ((t + 1) >> 1) : centre - (t >> 1); }
 
 // Pass 2.  Waves are independent (no workgroup barrier): KNN_WAVES of them share a workgroup only to fill a CU.
+// Non-finite input costs nothing per candidate.  Pass 1 stored every NaN coordinate as +inf, so a record's coordinates are
+// finite or infinite.  A query with finite coordinates then gets d = +inf from a record with an infinite one (finite - inf
+// squares to +inf, and a sum of squares has no inf - inf) and never a NaN; med3 and min drop a +inf because the triple
+// never exceeds FLT_MAX.  A query with an infinite coordinate gets +inf or NaN (inf - inf) from every record, and its triple
+// is still (FLT_MAX, FLT_MAX, FLT_MAX) whenever a NaN arrives: med3(FLT_MAX, FLT_MAX, NaN) = FLT_MAX under either rule.
 GS2M_KERNEL void __launch_bounds__(64 * KNN_WAVES)
 k_knn_search(int P, int groups, int supers, const float4* __restrict__ rec, const float4* __restrict__ box,
              const float4* __restrict__ sbox, float* __restrict__ out) {
@@ -188,7 +208,7 @@ k_knn_search(int P, int groups, int supers, const float4* __restrict__ rec, cons
 }
 
 static void knn_launch(hipStream_t stream, int P, const float* points, const int* order, const KnnScratch& s, float* out) {
-    GS2M_LAUNCH(k_knn_gather, dim3((unsigned)s.groups), dim3(KNN_GROUP), 0, stream, P, points, order, s.rec, s.box);
+    GS2M_LAUNCH(k_knn_gather, dim3((unsigned)s.groups), dim3(KNN_GROUP), 0, stream, P, points, order, 1, s.rec, s.box);
     GS2M_LAUNCH(k_knn_super, dim3((unsigned)((s.supers + 63) / 64)), dim3(64), 0, stream, s.groups, s.supers,
                 (const float4*)s.box, s.sbox);
     const unsigned blocks = (unsigned)(((int64_t)P + 64 * KNN_WAVES - 1) / (64 * KNN_WAVES));

@@ -12,7 +12,7 @@
 // (bits(+inf), 0xffffffff) = (+inf, none): a candidate at d = +inf has a smaller key and replaces it (its j < 2^31), a NaN
 // has a larger key and never does, and the low word read as int32 is -1 while nothing has replaced it.
 //
-// Layout.  The references go through pass 1 of knn_kernels.h unchanged (k_knn_gather, k_knn_super: 16-byte records in
+// Layout.  The references go through pass 1 of knn_kernels.h with nan_as_inf = 0 (k_knn_gather, k_knn_super: 16-byte records in
 // `ref_order`, a box per 256 records, a super-box per 16 boxes).  Pass 2 gives every wave 64 consecutive queries of
 // `query_order`, one per lane.  A query has no group of its own, so the wave first looks for a place to start: the lanes
 // share out ALL super-boxes (R / 4096 of them), each takes the distance between a super-box and the box of the wave's
@@ -24,7 +24,7 @@
 // A group is skipped only when its box distance is > the lane's best d in every live lane (wave-uniform, and STRICT: a box
 // at a distance equal to the best may hold a smaller index at that same distance, which must win).  Lanes that did not
 // need a staged group compare its candidates anyway; every one of them is farther than their best and changes nothing.
-// Coordinates that are NaN never enter a box (fminf / fmaxf return the other operand), so a reference with a NaN
+// Coordinates that are NaN never enter a box (k_knn_gather leaves them out), so a reference with a NaN
 // coordinate may sit in a box that does not contain it: its d is NaN and it is never selected, wherever it is met.
 // A query with a NaN coordinate has d = NaN to everything; it asks for no group and keeps (+inf, none).
 #pragma once
@@ -127,7 +127,7 @@ k_nn_search(int Q, const float* __restrict__ queries, const int* __restrict__ qu
 static void nn_launch(hipStream_t stream, int Q, const float* queries, const int* query_order, int R, const float* refs,
                       const int* ref_order, const KnnScratch& s, float* out_d2, int* out_idx) {
     if (R > 0) {
-        GS2M_LAUNCH(k_knn_gather, dim3((unsigned)s.groups), dim3(KNN_GROUP), 0, stream, R, refs, ref_order, s.rec, s.box);
+        GS2M_LAUNCH(k_knn_gather, dim3((unsigned)s.groups), dim3(KNN_GROUP), 0, stream, R, refs, ref_order, 0, s.rec, s.box);
         GS2M_LAUNCH(k_knn_super, dim3((unsigned)((s.supers + 63) / 64)), dim3(64), 0, stream, s.groups, s.supers,
                     (const float4*)s.box, s.sbox);
     }

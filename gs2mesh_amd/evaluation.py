@@ -92,8 +92,12 @@ def sample_mesh(mesh_or_arrays, density, lib=None, device=None):
     triangle of non-zero area, in triangle order, its barycentric grid at ``density`` (``gs2m_mesh_sample_count`` /
     ``_emit``, bit-identical to the reference's ``sample_single_tri``).  ``mesh_or_arrays``: a ``mesh.TriangleMesh`` or
     ``(vertices [V,3], triangles [T,3])``.  Raises if a triangle names a vertex outside the mesh, if one triangle would take
-    more than 1 048 576 grid nodes or the mesh more than 2^31 - 1 samples (``density`` far too small for the mesh's units)."""
+    more than 1 048 576 grid nodes or the mesh more than 2^31 - 1 samples (``density`` far too small for the mesh's units),
+    and unless 0 < ``density`` < inf (the kernels would give every triangle an empty grid there; the reference fails in
+    ``int(n1)``)."""
     torch = _torch()
+    if not 0 < float(density) < float("inf"):
+        raise ValueError(f"sample_mesh: density must be positive and finite, got {density}")
     lib = lib or _lib.get()
     if hasattr(mesh_or_arrays, "vertices"):
         verts, tris = mesh_or_arrays.vertices, mesh_or_arrays.triangles

@@ -624,8 +624,14 @@ int gs2m_stereo_sgm(const uint8_t* left_rgb8, const uint8_t* right_rgb8, int wid
  * (submodules/simple-knn/simple_knn.cu:131-183).  The exact 3-NN, defined bit for bit:
  *   - d(i, j) = (dx * dx + dy * dy) + dz * dz in f32, every operation rounded on its own (no FMA);
  *   - "other" is by index: a duplicate of point i at distance 0 counts;
- *   - b0 <= b1 <= b2 the three smallest d(i, j), j != i, FLT_MAX where fewer than three exist;
+ *   - a candidate counts only if its d is below the current third best, which starts at FLT_MAX (the reference's
+ *     updateKBest, :132-145): a d(i, j) that is NaN or not below FLT_MAX never counts;
+ *   - b0 <= b1 <= b2 the three smallest counting d(i, j), j != i, FLT_MAX where fewer than three count;
  *   - out[i] = ((b0 + b1) + b2) / 3.0f  (so P = 3 gives about 1.13e38 and P <= 2 gives +inf, as the reference's arithmetic).
+ * Input that is not finite follows from that rule.  A point with a NaN or infinite coordinate has no counting d at all:
+ * it gets +inf (not NaN, and this is not an error), and it changes no other point's result.  A point so far away that
+ * d(i, j) overflows is a neighbour at "no distance": it contributes FLT_MAX, like a missing one, so a point with only two
+ * neighbours in reach gets about 1.13e38 and not +inf.  Subnormal d are kept, never flushed.
  *   points                  [P][3] f32 device
  *   order                   NULL, or [P] int32 device: a permutation of [0, P), position -> index, in which the points are
  *                           walked.  It affects the speed only (sort along a space-filling curve: whole groups of far points

@@ -47,7 +47,9 @@ def sample_mesh(vertices, triangles, density):
             status |= INDEX
             continue
         g = grid_counts(v[i0], v[i1], v[i2], density)
-        if g is not None and g[2] >= 0 and g[3] >= 0 and not (g[2] + 1) * (g[3] + 1) <= MAX_GRID:
+        with np.errstate(over="ignore"):
+            capped = g is not None and g[2] >= 0 and g[3] >= 0 and not (g[2] + 1) * (g[3] + 1) <= MAX_GRID
+        if capped:
             status |= CAP
             continue
         p = sample_triangle(v[i0], v[i1], v[i2], density)

@@ -149,6 +149,83 @@ def test_a_triangle_above_the_grid_cap_is_flagged_and_not_sampled(backend):
     check(backend, "under_cap", lambda: (v, np.arange(3, dtype=np.int32).reshape(1, 3)), 1.0 / 1023.5)
 
 
+ORDINARY = [[[1, 2, 3], [1.45, 2, 3], [1, 2.45, 3]],                                    # 1 sample at density 0.2
+            [[-300, 200, 650], [-299.1, 200.7, 650.2], [-300.4, 200.1, 651.3]]]         # 15
+
+
+def two_triangles():
+    return np.array(ORDINARY, np.float64).reshape(-1, 3), np.arange(6, dtype=np.int32).reshape(2, 3)
+
+
+# thr = density * sqrt(L1 L2 / A), N = floor(L / thr).  Density 0 and the two tiny ones: N = +inf or about 1e300, (N + 1)^2 is
+# not <= the cap: refused and flagged.  A negative one: N < 0; NaN: N is NaN; +inf and 1e300: N = 0, whose only node is at
+# c = 0.5 / 1e-7.  All of these: an empty grid, no flag, and emit writes the vertices alone.
+DENSITIES = {"zero": (0.0, stmt.CAP), "least_subnormal": (5e-324, stmt.CAP), "tiny": (1e-300, stmt.CAP), "minus_zero": (-0.0, 0),
+             "negative": (-0.2, 0), "nan": (float("nan"), 0), "inf": (float("inf"), 0), "minus_inf": (float("-inf"), 0),
+             "huge": (1e300, 0)}
+
+
+@pytest.mark.parametrize("name", sorted(DENSITIES))
+def test_a_density_that_is_not_an_ordinary_positive_number(backend, name):
+    density, status = DENSITIES[name]
+    c, p = check(backend, ("density", name), two_triangles, density)
+    assert _REF[("density", name)][5] == status and list(c) == [0, 0]
+    np.testing.assert_array_equal(bits(p), bits(two_triangles()[0]))
+    if name == "zero":                                           # the same mesh still samples at an ordinary density afterwards
+        c, p = check(backend, ("density", "ordinary"), two_triangles, 0.2)
+        assert list(c) == [1, 15]
+
+
+BAD_COORDINATES = {"nan": float("nan"), "inf": float("inf"), "minus_inf": float("-inf"), "overflowing_square": 1e200,
+                   "vanishing_square": 1e-200, "capped": 1e154}
+
+
+@pytest.mark.parametrize("name", sorted(BAD_COORDINATES))
+def test_a_vertex_coordinate_that_is_not_an_ordinary_number(backend, name):
+    """four triangles, the second with one coordinate replaced, once in each of its nine places: the others keep their
+    samples and their offsets.  NaN, +-inf and 1e200 (its square overflows: L = A = +inf, thr is NaN) give an empty grid;
+    1e154 still has a finite square, so N is about 1e150 and the triangle is refused; 1e-200 is simply 0 to the others."""
+    def make():
+        v = []
+        for k in range(9):
+            m = np.array([ORDINARY[0], ORDINARY[1], ORDINARY[1], ORDINARY[0]], np.float64)
+            m[2] += 0.5
+            m[1, k // 3, k % 3] = BAD_COORDINATES[name]
+            v.append(m)
+        v = np.array(v).reshape(-1, 3)
+        return v, np.arange(len(v), dtype=np.int32).reshape(-1, 3)
+    c, p = check(backend, ("coordinate", name), make, 0.2)
+    status = _REF[("coordinate", name)][5]
+    c = c.reshape(9, 4)
+    assert np.all(c[:, [0, 2, 3]] == [1, 15, 1])
+    assert status == (stmt.CAP if name == "capped" else 0)
+    if name == "vanishing_square":
+        assert np.all(c[:, 1] > 1000)
+    else:
+        assert np.all(c[:, 1] == 0)
+
+
+@pytest.mark.parametrize("scale,counts", [(1e-80, [1, 15]), (1e-160, [0, 0]), (1e-312, [0, 0])])
+def test_meshes_at_scales_where_products_go_subnormal(backend, scale, counts):
+    """1e-80: the squares of the cross product's components are subnormal (1e-320) and the grid is that of the ordinary scale;
+    1e-160: the squared edges are subnormal and those underflow, A = 0; 1e-312: the coordinates themselves are subnormal"""
+    def make():
+        v, t = two_triangles()
+        return v * scale, t
+    c, p = check(backend, ("scale", scale), make, 0.2 * scale)
+    assert list(c) == counts
+    v = make()[0]
+    assert np.all(v != 0) and (scale > 1e-300 or np.all(np.abs(v) < np.finfo(np.float64).tiny))
+    np.testing.assert_array_equal(bits(p[:6]), bits(v))
+
+
+@pytest.mark.parametrize("density", [0.0, -0.2, float("nan"), float("inf"), float("-inf"), -0.0])
+def test_the_python_wrapper_refuses_a_density_that_is_not_positive_and_finite(backend, density):
+    from gs2mesh_amd import evaluation
+    with pytest.raises(ValueError, match="density"):
+        evaluation.sample_mesh(two_triangles(), density, lib=backend.lib)
+
+
 def test_the_python_wrapper_raises_on_every_flag(backend):
     from gs2mesh_amd import evaluation
     v, t = edge_mesh()

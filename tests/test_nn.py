@@ -148,8 +148,27 @@ def nan_queries():
     return q, uniform(700, 15)
 
 
+def inf_refs():
+    r = uniform(1500, 16)
+    r[[0, 7, 300, 1499], [0, 1, 2, 0]] = [np.inf, -np.inf, np.inf, -np.inf]     # single coordinates
+    r[256:512, 1] = np.inf                                       # a whole group: its box is at infinity in y
+    return uniform(300, 17), r
+
+
+def inf_queries():
+    q = uniform(200, 18)
+    q[0] = [np.inf, 0, 0]
+    q[[63, 64, 130], [1, 2, 0]] = [-np.inf, np.inf, -np.inf]
+    q[131] = np.inf
+    r = uniform(700, 19)
+    r[0, 0] = np.inf                                             # inf - inf: a NaN d to the queries at +inf in x
+    r[300, 2] = -np.inf
+    return q, r
+
+
 SETS = {"same_points": same_points, "lattice_centres": lattice_centres, "clusters": clusters, "planar": planar,
-        "shifted": shifted, "outside": outside, "too_far": too_far, "nan_refs": nan_refs, "nan_queries": nan_queries}
+        "shifted": shifted, "outside": outside, "too_far": too_far, "nan_refs": nan_refs, "nan_queries": nan_queries,
+        "inf_refs": inf_refs, "inf_queries": inf_queries}
 
 
 @pytest.mark.parametrize("name", sorted(SETS))
@@ -173,6 +192,13 @@ def test_point_sets_that_stress_culling_ties_and_non_finite_values(backend, name
     if name == "nan_queries":
         bad = np.isnan(q).any(axis=1)
         assert bad.sum() == 5 and np.all(np.isposinf(d[bad])) and np.all(i[bad] == -1) and np.all(i[~bad] >= 0)
+    if name == "inf_refs":
+        assert np.all(np.isfinite(d)) and np.all(i >= 0) and np.all(np.isfinite(r[i]))       # an infinite reference is never the nearest
+    if name == "inf_queries":
+        bad = np.isinf(q).any(axis=1)
+        assert bad.sum() == 5 and np.all(np.isposinf(d[bad])) and np.all(np.isfinite(d[~bad]))
+        # +inf with a valid index: the smallest whose d is not NaN.  Reference 0 is at +inf in x, like queries 0 and 131
+        assert list(i[[0, 63, 64, 130, 131]]) == [1, 0, 0, 0, 1]
 
 
 def test_the_orders_never_change_a_bit(backend):

@@ -46,6 +46,24 @@ def test_distCUDA2_equals_the_statement(cases, P):
 
 
 @pytest.mark.gpu
+def test_distCUDA2_with_a_nan_row_equals_the_statement():
+    """1500 points take the Morton path, and morton_order sees a NaN bounding box: whatever permutation comes out of it, the
+    NaN row gets +inf and no other row changes (the contract of include/gs2mesh_amd.h)"""
+    from backends import use_host_memory
+    from gs2mesh_amd.simple_knn import _C
+    use_host_memory(False)
+    pts = np.random.default_rng(1500).uniform(-1, 1, (1500, 3)).astype(np.float32)
+    pts[700, 1] = np.nan
+    assert len(pts) >= _C.MORTON_MIN_P
+    ref = knn_statement.mean_dist2(pts)
+    keep = np.arange(1500) != 700
+    np.testing.assert_array_equal(bits(ref[keep]), bits(knn_statement.mean_dist2(pts[keep])))
+    out = _C.distCUDA2(torch.from_numpy(pts).cuda()).cpu().numpy()
+    assert np.isposinf(out[700]) and np.all(np.isfinite(out[keep]))
+    np.testing.assert_array_equal(bits(out), bits(ref))
+
+
+@pytest.mark.gpu
 def test_a_cpu_tensor_is_an_error():
     from backends import use_host_memory
     from gs2mesh_amd.simple_knn import _C
