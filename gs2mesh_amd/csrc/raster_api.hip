@@ -583,6 +583,56 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
     return 0;
 }
 
+// Depth and opacity maps of the last gs2m_rasterize_forward on this handle (raster_depth.h): one kernel over the kept records,
+// lists and ranges.  Nothing of the state is written, so a gs2m_rasterize_backward may follow.  No host wait: the overflow word is
+// the host-mapped status the forward's tile scan wrote, read as it stands (current after any synchronisation of the stream, which
+// gs2m_raster_status is); the kernel clamps every range to the arena, so an unreported overflow reads nothing out of bounds.
+extern "C" int gs2m_rasterize_depth(gs2m_raster* r, int width, int height, float* depth_expected, float* depth_median,
+                                    float* alpha, gs2m_stream stream) {
+    if (!r) {
+        gs2m_set_error("null handle");
+        return 1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    GS2M_HIPCHK(hipSetDevice(r->device));
+    if (!r->fw_valid) {
+        gs2m_set_error("gs2m_rasterize_depth: the handle holds no state of a gs2m_rasterize_forward call (the last call was "
+                       "gs2m_render_views or gs2m_raster_reserve, or none)");
+        return 1;
+    }
+    if (width != r->fw_W || height != r->fw_H) {
+        gs2m_set_error("gs2m_rasterize_depth: %dx%d do not match the last forward (%dx%d)", width, height, r->fw_W, r->fw_H);
+        return 1;
+    }
+    if (r->fw_tile_rows != 1 || r->opt_tile_rows != 1) {
+        gs2m_set_error("gs2m_rasterize_depth needs the 16 x 16 instance lists: GS2M_OPT_TILE_ROWS 2 is not supported");
+        return 1;
+    }
+    if (r->opt_pair_batch > 1) {
+        gs2m_set_error("gs2m_rasterize_depth is not available with GS2M_OPT_PAIR_BATCH (a gs2m_render_views option)");
+        return 1;
+    }
+    const size_t bytes = sizeof(float) * (size_t)width * height;
+    if (r->fw_P == 0) {   // the forward rendered nothing: no pixel has a contributor
+        if (depth_expected) GS2M_HIPCHK(hipMemsetAsync(depth_expected, 0, bytes, st));
+        if (depth_median) GS2M_HIPCHK(hipMemsetAsync(depth_median, 0, bytes, st));
+        if (alpha) GS2M_HIPCHK(hipMemsetAsync(alpha, 0, bytes, st));
+        return 0;
+    }
+    if (r->h_status.get()[1].overflow) {
+        gs2m_set_error("gs2m_rasterize_depth: the forward overflowed its instance arena (gs2m_raster_status / gs2m_raster_reserve, then run it again)");
+        return 1;
+    }
+    if (!depth_expected && !depth_median && !alpha) return 0;
+    const int P = r->fw_P;
+    const int gx = (width + GS2M_TILE - 1) / GS2M_TILE, gy = (height + GS2M_TILE - 1) / GS2M_TILE;
+    const GeomRecs recs{r->d_recs.get(), r->d_recs.get() + 2 * (size_t)P};
+    gs2m_launch_blend_depth(st, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, P, r->last_cap, width, height, depth_expected,
+                            depth_median, alpha);
+    if (dbg_check(r, st, "blend depth")) return 1;
+    return 0;
+}
+
 extern "C" int gs2m_raster_backward_rows(gs2m_raster* r, int64_t* rows, int64_t* arena_bytes) {
     if (!r) {
         gs2m_set_error("null handle");

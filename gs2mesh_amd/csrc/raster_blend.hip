@@ -1,6 +1,7 @@
 // raster_blend.hip -- compositing stage (default FMA contraction; VALU-bound inner loop).
 #include "raster_blend.h"
 #include "raster_backward_blend.h"
+#include "raster_depth.h"
 #include "raster_internal.h"
 
 // gy = rows of the 16 x 16 reference grid; tile_rows = 16 x 16 tiles per instance list (GS2M_OPT_TILE_ROWS)
@@ -54,4 +55,13 @@ void gs2m_launch_blend_backward(hipStream_t st, int gx, int gy, const unsigned l
     const int tiles = gx * gy;
     GS2M_LAUNCH((k_blend_backward<4>), dim3((tiles + 3) / 4), dim3(256), 0, st, keys, tile_start, recs, cams, P, cap, dL_dpix,
                 row_offset, rows, n_rows);
+}
+
+// depth / opacity maps of the last single-view forward (16 x 16 lists): one wave per tile, four tiles per workgroup
+void gs2m_launch_blend_depth(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
+                             GeomRecs recs, int P, unsigned cap, int W, int H, float* depth_expected, float* depth_median,
+                             float* alpha) {
+    const int tiles = gx * gy;
+    GS2M_LAUNCH((k_blend_depth<4>), dim3((tiles + 3) / 4), dim3(256), 0, st, keys, tile_start, recs, P, cap, W, H, gx, gy,
+                depth_expected, depth_median, alpha);
 }

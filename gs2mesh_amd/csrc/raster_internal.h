@@ -62,3 +62,8 @@ void gs2m_launch_blend_backward(hipStream_t st, int gx, int gy, const unsigned l
                                 const unsigned* row_offset, float* rows, unsigned long long n_rows);
 void gs2m_launch_gaussian_backward(hipStream_t st, const GaussIn& g, const CamUniform* cams, GeomRecs recs,
                                    const unsigned* row_offset, const float* rows, unsigned long long n_rows, const BwOut& out);
+
+// ---- depth / opacity maps (gs2m_rasterize_depth): [H,W] f32 each, any of them null
+void gs2m_launch_blend_depth(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
+                             GeomRecs recs, int P, unsigned cap, int W, int H, float* depth_expected, float* depth_median,
+                             float* alpha);

@@ -170,6 +170,7 @@ class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()
         self.raster_settings = raster_settings
+        self._last = None    # what depth_maps() needs of the last forward: its inputs, the handle and the handle's call count
 
     def markVisible(self, positions):
         # Mark visible points (based on frustum culling for camera) with a boolean
@@ -198,5 +199,25 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = torch.Tensor([])
         # Invoke the HIP rasterization routine
-        return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, raster_settings)
+        out = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                  cov3D_precomp, raster_settings)
+        h = _handle(means3D.device)
+        self._last = (h, h.state_calls, (means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp))
+        return out
+
+    def depth_maps(self, want=("expected", "median", "alpha")):
+        """Extension (the reference has no depth output): maps of THIS rasteriser's last ``forward`` as a dict of [H,W] float32
+        tensors -- ``expected`` (alpha-weighted mean view-space z of the contributing Gaussians' centres), ``median`` (z of the
+        contributor that takes the transmittance to 0.5 or below) and ``alpha`` (accumulated opacity); 0 = no contributor
+        (``gs2m_rasterize_depth``).  If another forward ran on the device's handle since, this one is replayed first into a
+        scratch image, the way the backward pass does.  The results are DETACHED: no gradient flows through depth or alpha."""
+        if self._last is None:
+            raise RuntimeError("GaussianRasterizer.depth_maps: this rasteriser has not run a forward")
+        h, calls, inputs = self._last
+        rs = self.raster_settings
+        with torch.no_grad():
+            if h.state_calls != calls:
+                means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp = inputs
+                _forward(h, rs, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, _none_if_empty)
+                self._last = (h, h.state_calls, inputs)
+            return h.depth_maps(int(rs.image_width), int(rs.image_height), want=want, like=_f32c(rs.bg))

@@ -17,8 +17,12 @@ def _dev(x, device):
     return torch.as_tensor(x, dtype=torch.float32, device=device).contiguous()
 
 
-def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None):
-    """Background tensor (bg_color) must be on the GPU, as in the reference."""
+def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, return_depth=False):
+    """Background tensor (bg_color) must be on the GPU, as in the reference.  ``return_depth=True`` (an extension: the reference
+    renders colour only) adds three detached [H,W] maps of the same forward to the dict: ``depth`` (alpha-weighted mean
+    view-space z of the contributing Gaussians' centres), ``median_depth`` (z of the contributor that takes the transmittance
+    to one half) and ``alpha`` (accumulated opacity; render = C + (1 - alpha) * bg); 0 = no contributor.  No gradient flows
+    through them."""
     device = pc.get_xyz.device
     tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
     tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
@@ -65,5 +69,9 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         rendered_image, radii = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs,
                                            colors_precomp=colors_precomp, opacities=opacity, scales=scales,
                                            rotations=rotations, cov3D_precomp=cov3D_precomp)
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii}
+    out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+           "radii": radii}
+    if return_depth:
+        maps = rasterizer.depth_maps()
+        out.update(depth=maps["expected"], median_depth=maps["median"], alpha=maps["alpha"])
+    return out

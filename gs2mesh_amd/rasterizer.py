@@ -235,6 +235,28 @@ class Rasterizer:
             self._lib)
         return g
 
+    def depth_maps(self, W, H, want=("expected", "median", "alpha"), like=None, stream=None):
+        """``gs2m_rasterize_depth``: maps of the LAST ``forward`` on this handle (``state_calls`` tells whether another
+        ``forward`` / ``render_views`` / ``reserve`` ran since).  -> dict of freshly allocated [H,W] float32 arrays, one per name
+        in ``want``: ``expected`` (alpha-weighted mean view-space z of the contributing Gaussians' centres), ``median`` (z of the
+        contributor that takes the transmittance to 0.5 or below) and ``alpha`` (accumulated opacity, 1 - T); 0 = no
+        contributor in all three.  Asynchronous.  ``like``: a tensor on the device the maps go to (default: this handle's
+        device)."""
+        names = ("expected", "median", "alpha")
+        unknown = [w for w in want if w not in names]
+        if unknown:
+            raise ValueError(f"depth_maps: unknown map(s) {unknown}; known: {names}")
+        shape = (int(H), int(W))
+        if like is not None:
+            out = {k: _empty(like, shape, np.float32) for k in names if k in want}
+        else:
+            out = {k: _lib.MEMORY.empty(shape, np.float32, self.device) for k in names if k in want}
+        some = next(iter(out.values()), None)
+        st = _stream_of(like if like is not None else some, stream)
+        _lib.check(self._lib.gs2m_rasterize_depth(self._h, int(W), int(H), _ptr(out.get("expected")), _ptr(out.get("median")),
+                                                  _ptr(out.get("alpha")), st), self._lib)
+        return out
+
     def backward_rows(self):
         """-> (instance rows of the last ``backward``, bytes of the handle's row arena; 0 = never allocated)."""
         rows, nbytes = C.c_int64(0), C.c_int64(0)

@@ -197,6 +197,17 @@ class Renderer:
             self._views[camera_number] = out
         return self._views[camera_number]
 
+    def left_view(self, camera_number):
+        """(3DGS ``Camera`` of the left eye, GaussianModel, background tensor): what ``gaussian_renderer.render`` takes.  The
+        camera is the one ``_pair`` builds for ``render_views``.  For ``depth_utils.RenderedDepth``."""
+        if self._raster is None:
+            raise RuntimeError("call prepare_renderer() first")
+        c = self.cameras[camera_number]['left']
+        R, T = convert_R_T_to_GS(tuple(c['rot']), tuple(c['pos']))
+        w, h = c['width'], c['height']
+        cam = Camera(0, R, T, 2 * np.arctan2(w, 2 * c['fx']), 2 * np.arctan2(h, 2 * c['fy']), w, h)
+        return cam, self.gaussians, self.background
+
     def render_pair_device(self, camera_number, want_color=False):
         """In-memory hand-off: dict(rgb8=[2,H,W,3] u8 device tensor (left, right), color=[2,3,H,W] f32)."""
         if self._raster is None:

@@ -220,6 +220,39 @@ int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int R, const fl
 /* Instance rows of the last gs2m_rasterize_backward call and the bytes of the row arena (0: never allocated). */
 int gs2m_raster_backward_rows(gs2m_raster* r, int64_t* rows, int64_t* arena_bytes);
 
+/*
+ * Depth and opacity maps of the LAST gs2m_rasterize_forward on this handle.  An extension: the reference's renderCUDA writes
+ * colour only.  One kernel walks the kept per-tile lists front to back with the alpha function of the backward pass
+ * (csrc/raster_depth.h) and takes renderCUDA's three decisions per pixel.  Per pixel, T = 1, S = 0, Z = 0, med = 0; for every
+ * instance j of the tile's list in order:
+ *     skip j if power > 0 or alpha < 1/255, with alpha = min(0.99, o G)
+ *     T' = T (1 - alpha); if T' < 1e-4 the pixel is finished, BEFORE accumulating (forward.cu:345-350)
+ *     w = alpha T;  S += w;  Z += w z_j;  T = T';   if med == 0 and T <= 0.5: med = z_j
+ * z_j is the view-space z of the Gaussian's CENTRE (the depth of the sort key), not a ray-surface intersection.
+ *
+ *   depth_expected[H,W]  device or NULL: S > 0 ? Z / S : 0    (alpha-weighted mean z of the contributors)
+ *   depth_median[H,W]    device or NULL: med                  (z of the contributor that takes T to 0.5 or below)
+ *   alpha[H,W]           device or NULL: 1 - T                (the forward's image is C + (1 - alpha) bg)
+ * Every non-NULL output is written completely, with plain stores, each pixel once: two calls give identical bits.  A pixel
+ * without a contributor holds exactly 0 in all three; listed Gaussians have z > 0.2, so 0 means "no depth" (what the TSDF
+ * integrator treats as invalid).  1 - T is exact for T in [0.5, 1]: depth_median > 0 exactly where alpha >= 0.5.  The handle's
+ * state is only read: a gs2m_rasterize_backward may follow.  No gradient flows through these maps.
+ *
+ * Errors, as gs2m_rasterize_backward: no gs2m_rasterize_forward state in the handle (e.g. after gs2m_render_views or
+ * gs2m_raster_reserve), width / height different from that call, GS2M_OPT_TILE_ROWS 2, GS2M_OPT_PAIR_BATCH > 1, an overflowed
+ * forward.  GS2M_OPT_EXACT_TILE_CULL 0 / 1 / 2 give the same bits (a culled instance has alpha < 1/255 on its whole tile).
+ * Asynchronous, no host wait: the overflow flag is the forward's host-mapped status word as it stands, i.e. current once
+ * the stream has been synchronised after the forward (gs2m_raster_status does); the kernel clamps every list range to the
+ * arena, so a call on an overflow not yet visible reads nothing out of bounds and its maps are as invalid as the image.
+ *
+ * STATED TOLERANCE: against an fp64 statement of the walk above (tests/depth_statement.py), on pixels without a threshold
+ * decision within 1e-4 and without a transmittance within 1e-4 of 0.5, alpha and depth_expected are within 4 x the error of
+ * the SAME statement evaluated in fp32, in max|x - x64| / max|x64| and in relative L2, and depth_median is bit-equal to the
+ * fp32 view-space z of the statement's median Gaussian (tests/test_raster_depth.py; figures: profiles/raster_depth.txt).
+ */
+int gs2m_rasterize_depth(gs2m_raster* r, int width, int height, float* depth_expected, float* depth_median,
+                         float* alpha, gs2m_stream stream);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:26-31,
  * rasterizer_impl.cu:54-66,141-153).  present[P]: device, 1 byte per Gaussian. */
 int gs2m_mark_visible(int P, const float* means3D, const float* viewmatrix,

@@ -1,0 +1,144 @@
+"""Cost of depth without a matcher on a C2-shaped job (300 k Gaussians, 1600 x 1200).
+
+  python tools/depth_bench.py [--reps 50] [--repeats 5] [--views 16] [--out profiles/raster_depth_bench.json]
+
+  * the depth pass (gs2m_rasterize_depth: all three maps of one view), in us per view, and gs2m_rasterize_forward as a whole:
+    stream events around `reps` calls after a warm-up, `repeats` times (median and range: the spread comes with the figure);
+  * RenderedDepth.run(keep_on_device=True, write_files=False) + TSDF.run(fuse="batch") over `views` ring cameras, in views/s:
+    a host clock around work that ends in the mesh download, after one warm-up pass of the same shapes.
+Prints one JSON object.  No speed gate: nothing of this had been measured before.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+from argparse import Namespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def tsdf_args():
+    return Namespace(TSDF_scale=1.0, TSDF_dilate=1, TSDF_valid=None, TSDF_skip=None, TSDF_use_occlusion_mask=True,
+                     TSDF_use_mask=False, TSDF_invert_mask=False, TSDF_erode_mask=True, TSDF_erosion_kernel_size=10,
+                     TSDF_closing_kernel_size=10, TSDF_voxel=2, TSDF_sdf_trunc=0.04, TSDF_min_depth_baselines=4,
+                     TSDF_max_depth_baselines=20, TSDF_cleaning_threshold=100000)
+
+
+def make_scene(cfg, views, root, device):
+    """the part of Renderer that RenderedDepth and TSDF read, for the config's synthetic splat on `views` ring cameras"""
+    import torch
+    from gs2mesh_amd import synthetic
+    from gs2mesh_amd.gaussian_model import GaussianModel
+    poses = synthetic.ring_poses(views, cfg.ring_radius)
+    baseline = cfg.ring_radius * cfg.baseline_pct / 100.0
+    scene = synthetic.DiskScene(root, poses, cfg.width, cfg.height, cfg.focal, baseline)
+    g = synthetic.synth_v1(cfg.P, cfg.seed, cfg.log_s_mu)
+    model = GaussianModel(3, device=device)
+    model.load_arrays(g["xyz"], g["features_dc"], g["features_rest"], g["scaling"], g["rotation"], g["opacity"])
+    background = torch.zeros(3, device=device)
+    cams = [synthetic.stereo_cameras(p, cfg.width, cfg.height, cfg.focal, cfg.focal, baseline)[0] for p in poses]
+    scene.left_view = lambda i: (cams[i], model, background)
+    return scene, model, cams
+
+
+def timed(fn, reps):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def spread(xs, digits):
+    return dict(median=round(statistics.median(xs), digits), min=round(min(xs), digits), max=round(max(xs), digits))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="C2")
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--views", type=int, default=16)
+    ap.add_argument("--max-blocks", type=int, default=131072, help="block pool of the fused volume (16^3 voxels, 64 KiB each)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("depth_bench: no HIP device (there is no CPU path)")
+    from gs2mesh_amd import synthetic
+    from gs2mesh_amd.depth_utils import RenderedDepth
+    from gs2mesh_amd.rasterizer import Rasterizer
+    from gs2mesh_amd.tsdf_utils import TSDF
+    cfg = synthetic.CONFIGS[a.config]
+    dev = torch.device("cuda:0")
+    root = tempfile.mkdtemp(prefix="depth_bench_")
+    scene, model, cams = make_scene(cfg, a.views, root, "cuda:0")
+    W, H = cfg.width, cfg.height
+    # ---- operator level: one view
+    t = lambda x: torch.as_tensor(x, dtype=torch.float32, device=dev).contiguous()
+    cam = cams[0]
+    common = (t(cam.world_view_transform), t(cam.full_proj_transform), t(cam.camera_center), torch.zeros(3, device=dev), W, H,
+              cam.tanfovx, cam.tanfovy)
+    with torch.no_grad():
+        xyz, opac = model.get_xyz.contiguous(), model.get_opacity.reshape(-1).contiguous()
+        kw = dict(shs=model.get_features.contiguous(), scales=model.get_scaling.contiguous(),
+                  rotations=model.get_rotation.contiguous(), sh_degree=3)
+    r = Rasterizer(0)
+    fwd = lambda sync=False: r.forward(xyz, opac, *common, sync=sync, **kw)
+    depth = lambda: r.depth_maps(W, H, like=xyz)
+    fwd(sync=True)      # sizes the instance arena
+    instances = int(r.last_num_rendered)
+    for _ in range(3):
+        fwd()
+        depth()
+    m = depth()
+    torch.cuda.synchronize()
+    covered = float((m["alpha"] >= 0.5).float().mean())
+    t_fwd = [timed(fwd, a.reps) * 1e3 for _ in range(a.repeats)]
+    t_depth = [timed(depth, a.reps) * 1e3 for _ in range(a.repeats)]
+    t_one = [timed(lambda: r.depth_maps(W, H, want=("median",), like=xyz), a.reps) * 1e3 for _ in range(a.repeats)]
+    # ---- pipeline level: RenderedDepth -> TSDF over the ring
+    args = tsdf_args()
+
+    def job():
+        rd = RenderedDepth(root, scene, args)
+        t0 = time.perf_counter()
+        rd.run(keep_on_device=True, write_files=False)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        fuse = TSDF(scene, rd, args, "out", frame_source=rd.frame_source, max_blocks=a.max_blocks, fuse="batch")
+        fuse.run()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        return t1 - t0, t2 - t1, int(fuse.mesh.triangles.shape[0]), int(fuse.volume.num_blocks)
+
+    res = dict(config=a.config, P=cfg.P, width=W, height=H, instances=instances, pixels_with_median=round(covered, 4),
+               reps=a.reps, repeats=a.repeats, forward_us=spread(t_fwd, 1), depth_pass_us=spread(t_depth, 1),
+               depth_pass_median_only_us=spread(t_one, 1),
+               depth_over_forward=round(statistics.median(t_depth) / statistics.median(t_fwd), 3), views=a.views)
+    try:
+        job()           # warm-up: every shape of the timed window
+        runs = [job() for _ in range(max(a.repeats, 1))]
+        res.update(render_views_per_s=spread([a.views / x[0] for x in runs], 1),
+                   fuse_views_per_s=spread([a.views / x[1] for x in runs], 1),
+                   render_and_fuse_views_per_s=spread([a.views / (x[0] + x[1]) for x in runs], 1), triangles=runs[-1][2],
+                   blocks=runs[-1][3], max_blocks=a.max_blocks)
+    except RuntimeError as e:       # a volume overflow (raise --max-blocks) must not lose the operator-level figures
+        res["pipeline_error"] = str(e)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
