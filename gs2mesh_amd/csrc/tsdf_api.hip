@@ -41,6 +41,7 @@ struct gs2m_tsdf {
     int timing = 0;
     EventPool events;                      // weight = frames the timed launch covered (a batch counts as that many launches)
     DeviceBuffer<TsdfBatchFrame> d_bframes;   // [GS2M_TSDF_MAX_BATCH] frame descriptors of the batch in flight
+    DeviceBuffer<float> d_tiles;              // the batch's max-depth map (tsdf_common.h): grow-only, GS2M_TSDF_MAX_BATCH frames of the largest image seen
     // pinned staging ring for the descriptors (a pageable source would make the "async" copy wait for the stream)
     static const int kRing = 8;
     PinnedBuffer<TsdfBatchFrame> h_bframes;   // [kRing][GS2M_TSDF_MAX_BATCH]
@@ -304,6 +305,8 @@ extern "C" int gs2m_tsdf_integrate_batch(gs2m_tsdf* t, int n_frames, const float
         return 1;
     GS2M_HIPCHK(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
+    // sized for a full batch on the first use of an image size, so that a later, longer sweep of such images allocates nothing
+    if (n_frames > 0 && t->d_tiles.reserve_exact((size_t)GS2M_TSDF_MAX_BATCH * GS2M_TSDF_TILES(width) * GS2M_TSDF_TILES(height))) return 1;
     for (int f0 = 0; f0 < n_frames; f0 += GS2M_TSDF_MAX_BATCH) {
         const int nf = n_frames - f0 < GS2M_TSDF_MAX_BATCH ? n_frames - f0 : GS2M_TSDF_MAX_BATCH;
         // next slot of the pinned staging ring; its previous copy (kRing batches ago) has long completed
@@ -331,11 +334,11 @@ extern "C" int gs2m_tsdf_integrate_batch(gs2m_tsdf* t, int n_frames, const float
         GS2M_HIPCHK(hipMemsetAsync(t->V.counters + 3, 0, sizeof(unsigned), st));  // work counter of the batch sweep
         {   // a batch counts as nf launches of each stage: the averages stay per frame
             StageTimer tm(t->events, t->timing != 0, st, 0, "gs2m:tsdf_touch_batch", nf);
-            gs2m_launch_tsdf_touch_batch(st, t->V, hb[0].f, nf, t->d_bframes.get());
+            gs2m_launch_tsdf_touch_batch(st, t->V, hb[0].f, nf, t->d_bframes.get(), t->d_tiles.get());
         }
         {
             StageTimer tm(t->events, t->timing != 0, st, 1, "gs2m:tsdf_integrate_batch", nf);
-            gs2m_launch_tsdf_integrate_batch(st, t->n_cu, t->V, t->d_bframes.get());
+            gs2m_launch_tsdf_integrate_batch(st, t->n_cu, t->V, t->d_bframes.get(), t->d_tiles.get());
         }
     }
     return 0;

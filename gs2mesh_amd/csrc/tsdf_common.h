@@ -41,11 +41,11 @@ struct TsdfVolume {  // device pointers + sizes, passed by value
     int has_color;
 };
 
-struct TsdfFrame {  // per-frame uniforms, passed by value in the launch packet
+struct alignas(16) TsdfFrame {  // per-frame uniforms, passed by value in the launch packet
+    float E[12];  // (float)extrinsic rows 0..2.  First and 16-byte aligned: the sweep's cull test reads it per lane, as three float4
     double pose[12];  // camera->world, rows 0..2 of inverse(extrinsic)
     double fx, fy, cx, cy;
     double unit_length, sdf_trunc, depth_trunc;
-    float E[12];  // (float)extrinsic rows 0..2
     float fx_f, fy_f, cx_f, cy_f, fx_inv_f, fy_inv_f;
     float voxel_length_f, half_voxel_length_f, sdf_trunc_f, sdf_trunc_inv_f;
     float Es02, Es12, Es22;  // E[:,2] * voxel_length (incremental z step)
@@ -66,6 +66,11 @@ struct TsdfBatchFrame {
     const unsigned char* mask;
 };
 #define GS2M_TSDF_MAX_BATCH 64   // frames per batch: one bit per frame in the per-block touch mask
+// The batch sweep's max-depth map: one float per frame and tile of GS2M_TSDF_TILE^2 pixels (tile counts rounded up), the largest
+// valid depth of the tile as the integrator sees it, 0 where it has none.  [frame][tile row][tile column].
+#define GS2M_TSDF_TILE 8
+#define GS2M_TSDF_TILES(n) (((n) + GS2M_TSDF_TILE - 1) / GS2M_TSDF_TILE)
+#define GS2M_TSDF_CULL_MAX_TILES 48   // a footprint over more tiles than this is not tested: the pass runs
 
 // device-internal voxel index (see header); host code uses the same formula in gs2m_tsdf_download
 #define GS2M_TSDF_VINDEX(x, y, z) (((((z) >> 2) * 16 + ((x) >> 2) * 4 + ((y) >> 2)) * 64) + ((z)&3) * 16 + ((x)&3) * 4 + ((y)&3))

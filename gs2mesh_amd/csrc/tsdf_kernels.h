@@ -55,9 +55,12 @@ GS2M_DEVICE float tsdf_distance_multiplier(const TsdfFrame& f, int u, int v) {
 }
 // Depth as the integrator sees it (tsdf_utils.py:68-93 + Image::ConvertDepthToFloatImage), in two halves: the load with
 // TSDF.run's mask, then the conversion.  The batch sweep runs them a frame apart, everything else back to back.
+GS2M_DEVICE float tsdf_mask_depth(float d, unsigned mask_byte) {
+    return mask_byte == 0u ? d * 0.0f : d;                   // depth = depth * mask  (a NaN or infinite depth stays NaN)
+}
 GS2M_DEVICE float tsdf_read_depth(const TsdfFrame& f, const float* __restrict__ depth, const unsigned char* __restrict__ mask, size_t pix) {
     float d = depth[pix];
-    if (f.use_mask && mask[pix] == 0) d = d * 0.0f;          // depth = depth * mask  (a NaN or infinite depth stays NaN)
+    if (f.use_mask) d = tsdf_mask_depth(d, mask[pix]);
     return d;
 }
 GS2M_DEVICE float tsdf_convert_depth(const TsdfFrame& f, float d) {
@@ -276,13 +279,7 @@ k_tsdf_touch(TsdfVolume V, TsdfFrame f, const float* __restrict__ depth, const u
     tsdf_touch_body(V, f, depth, mask, stage_all, -1);
 }
 
-// batch mode: blockIdx.y = frame of the batch
-GS2M_KERNEL void __launch_bounds__(256)
-k_tsdf_touch_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) {
-    __shared__ TouchStage stage_all[4];
-    const TsdfBatchFrame& bf = frames[blockIdx.y];
-    tsdf_touch_body(V, bf.f, bf.depth, bf.mask, stage_all, (int)blockIdx.y);
-}
+// batch mode: k_tsdf_touch_batch, below the sweep's max-depth map it also builds
 
 
 // Compacts the hash cells stamped in this frame into V.touched (order = hash order).
@@ -442,8 +439,178 @@ k_tsdf_integrate(TsdfVolume V, TsdfFrame f, const float* __restrict__ depth, con
 // at a time by the four waves of the workgroup ("frame lanes": LDS exchange + barrier per round, one voxel of state per thread)
 // 30 -> 80 us per frame -- the dependent round trips only move from the frame loop to a loop over x-quarters; the colour gathered
 // together with the depth (one round trip per frame instead of two dependent ones, but for every probed voxel) 30.5 -> 35.2.
+// The kernel itself follows the cull test it runs per work item:
+//
+// Frame passes proven dead by a max-depth map.  The touch rule marks every block in the +-sdf_trunc box of a depth sample, so
+// many marked blocks lie beside the silhouette (every depth they see is 0) or wholly behind the band (every sdf <= -trunc):
+// tools/tsdf_dead_pass_census.py counts 39 % (C2) and 30 % (C4) of the benchmark's wave passes as provably dead.  A culled pass
+// issues no gather at all.
+//
+// The map, once per batch (k_tsdf_touch_batch): per frame and tile of 8 x 8 pixels the largest depth the integrator would accept (d > 0
+// after mask, min_depth, depth_scale and depth_trunc; NaN, negative, zero, masked and truncated samples are no samples), 0 for a
+// tile without one.  A wave takes 256 columns x 8 rows = 32 tiles, a workgroup four such spans side by side.  The kernel streams
+// every depth image of the batch once, so it reads 16 bytes per lane where the rows allow it (the width a multiple of 4, the
+// image 16-byte and the mask 4-byte aligned: 4 columns per lane, two lanes per tile, 8 loads in flight) and one float per lane
+// in four 64-column steps otherwise.
+GS2M_DEVICE float tsdf_tile_sample(const TsdfFrame& f, float m, float raw) {
+    const float d = tsdf_convert_depth(f, raw);
+    return d > 0.0f && d > m ? d : m;   // tsdf_decide's own test of a sample: a NaN never gets in
+}
+// tile row `ty` of frame `bf`, columns from 1024 * `bx`: `out` = that row of the frame's map
+GS2M_DEVICE void tsdf_depth_tiles_body(const TsdfBatchFrame& bf, float* __restrict__ out, int bx, int ty) {
+    const TsdfFrame& f = bf.f;
+    const float* __restrict__ depth = bf.depth;
+    const unsigned char* __restrict__ mask = bf.mask;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int xw = (bx * 4 + (int)(threadIdx.x >> 6)) * 256;   // the wave's first column
+    if (xw >= f.W) return;                                      // wave-uniform
+    const int y0 = ty * GS2M_TSDF_TILE;
+    const bool wide = (f.W & 3) == 0 && ((size_t)depth & 15u) == 0u && (!f.use_mask || ((size_t)mask & 3u) == 0u);
+    if (wide) {
+        const int x = xw + 4 * lane;
+        float m = 0.0f;
+        if (x < f.W) {
+            float4 raw[GS2M_TSDF_TILE];
+            unsigned mk[GS2M_TSDF_TILE];
+#pragma unroll
+            for (int r = 0; r < GS2M_TSDF_TILE; ++r) {
+                const int y = y0 + r < f.H ? y0 + r : f.H - 1;   // below the image: the last row again
+                const size_t pix = (size_t)y * f.W + x;
+                raw[r] = *reinterpret_cast<const float4*>(depth + pix);
+                mk[r] = f.use_mask ? *reinterpret_cast<const unsigned*>(mask + pix) : 0xffffffffu;
+            }
+#pragma unroll
+            for (int r = 0; r < GS2M_TSDF_TILE; ++r) {
+                m = tsdf_tile_sample(f, m, tsdf_mask_depth(raw[r].x, mk[r] & 0xffu));
+                m = tsdf_tile_sample(f, m, tsdf_mask_depth(raw[r].y, (mk[r] >> 8) & 0xffu));
+                m = tsdf_tile_sample(f, m, tsdf_mask_depth(raw[r].z, (mk[r] >> 16) & 0xffu));
+                m = tsdf_tile_sample(f, m, tsdf_mask_depth(raw[r].w, mk[r] >> 24));
+            }
+        }
+        const float o = gs2m_shfl_xor(m, 1);   // every lane takes part, also those right of the image (m = 0)
+        if (o > m) m = o;
+        if ((lane & 1) == 0 && x < f.W) out[x / GS2M_TSDF_TILE] = m;
+        return;
+    }
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) {
+        const int x = xw + 64 * i + lane;
+        float m = 0.0f;
+        if (x < f.W) {
+#pragma unroll
+            for (int r = 0; r < GS2M_TSDF_TILE; ++r) {
+                const int y = y0 + r < f.H ? y0 + r : f.H - 1;
+                m = tsdf_tile_sample(f, m, tsdf_read_depth(f, depth, mask, (size_t)y * f.W + x));
+            }
+        }
+#pragma unroll
+        for (int s = 1; s < GS2M_TSDF_TILE; s <<= 1) {
+            const float o = gs2m_shfl_xor(m, s);
+            if (o > m) m = o;
+        }
+        if ((lane & (GS2M_TSDF_TILE - 1)) == 0 && x < f.W) out[x / GS2M_TSDF_TILE] = m;
+    }
+}
+
+// The touch pass of a batch and its map in ONE launch: blockIdx.y = frame of the batch; the first `n_touch` workgroups of a
+// frame run the touch pass (bound by the latency of its hash probes), the others stream the frame's depth image into the map
+// (bound by bandwidth), `map_wg_x` workgroups per tile row.  Both only read the images, neither reads what the other writes.
 GS2M_KERNEL void __launch_bounds__(256)
-k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) {
+k_tsdf_touch_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames, unsigned n_touch, float* __restrict__ tiles, int tiles_x,
+                   int tiles_y, unsigned map_wg_x) {
+    __shared__ TouchStage stage_all[4];
+    const TsdfBatchFrame& bf = frames[blockIdx.y];
+    if (blockIdx.x < n_touch) {
+        tsdf_touch_body(V, bf.f, bf.depth, bf.mask, stage_all, (int)blockIdx.y);
+    } else {
+        const unsigned m = blockIdx.x - n_touch, ty = m / map_wg_x;
+        tsdf_depth_tiles_body(bf, tiles + ((size_t)blockIdx.y * tiles_y + ty) * tiles_x, (int)(m - ty * map_wg_x), (int)ty);
+    }
+}
+
+// Can frame `e4` (its E, three float4) update a voxel of the micro-column x in [xa, xb], y in [ya, yb] (voxel centres, world),
+// z = z0 .. z0 + 15 voxels?  false only with a proof that it cannot:
+//   * all 8 corner centres lie in front of the camera, so the column projects into the hull of its projected corners;
+//   * F = the bounding box of the 8 projections, widened by mu >= 1 pixel (the + 0.5f truncation of tsdf_project, and the
+//     distance of any voxel's computed point from the hull of these corners, below) and clipped to the image, is empty -- no
+//     voxel sees a pixel -- or holds no depth sample (Dmax = the largest tile value over F is 0), or
+//   * Dmax - zlow <= -sdf_trunc, zlow = the least corner z lowered by a voxel length and eps.
+// tsdf_decide updates iff d > 0 && (d - zc) * mult > -trunc; every voxel of the column has d <= Dmax and zc >= zlow, fp32
+// subtraction and multiplication are monotone and mult = sqrtf(1 + ...) >= 1 does not raise a difference that is <= 0: a
+// culled pass would have updated nothing, and the volume keeps the bits of the uncut sweep.
+// eps bounds how far a point the sweep computes (tsdf_cam_point, then up to 15 tsdf_z_steps: < 24 roundings of at most
+// 2^-24 S each, S = the sum of the magnitudes of the terms) and a corner computed here (< 10 such) lie from the exact affine
+// image of the voxel centre: 2^-18 S for both together.  A pose with a NaN or an infinity fails a comparison and is live.
+GS2M_DEVICE bool tsdf_pass_live(const TsdfFrame& f0, const float4* __restrict__ e4, const float* __restrict__ tiles, int tiles_x,
+                                float xa, float xb, float ya, float yb, float z0) {
+    const float4 r0 = e4[0], r1 = e4[1], r2 = e4[2];
+    const float vl = f0.voxel_length_f, zspan = 15.0f * vl;
+    const float ax = fmaxf(fabsf(xa), fabsf(xb)), ay = fmaxf(fabsf(ya), fabsf(yb)), az = fabsf(z0) + zspan + vl;
+    const float S = fmaxf(fmaxf(fabsf(r0.x) * ax + fabsf(r0.y) * ay + fabsf(r0.z) * az + fabsf(r0.w),
+                                fabsf(r1.x) * ax + fabsf(r1.y) * ay + fabsf(r1.z) * az + fabsf(r1.w)),
+                          fabsf(r2.x) * ax + fabsf(r2.y) * ay + fabsf(r2.z) * az + fabsf(r2.w));
+    const float eps = S * (1.0f / 262144.0f);
+    const float bx = r0.x * xa + r0.y * ya + r0.z * z0 + r0.w, by = r1.x * xa + r1.y * ya + r1.z * z0 + r1.w,
+                bz = r2.x * xa + r2.y * ya + r2.z * z0 + r2.w;
+    const float dx[3] = {r0.x * (xb - xa), r0.y * (yb - ya), r0.z * zspan};
+    const float dy[3] = {r1.x * (xb - xa), r1.y * (yb - ya), r1.z * zspan};
+    const float dz[3] = {r2.x * (xb - xa), r2.y * (yb - ya), r2.z * zspan};
+    float cx[8], cy[8], cz[8], zmin = bz;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        cx[c] = bx + ((c & 1) ? dx[0] : 0.0f) + ((c & 2) ? dx[1] : 0.0f) + ((c & 4) ? dx[2] : 0.0f);
+        cy[c] = by + ((c & 1) ? dy[0] : 0.0f) + ((c & 2) ? dy[1] : 0.0f) + ((c & 4) ? dy[2] : 0.0f);
+        cz[c] = bz + ((c & 1) ? dz[0] : 0.0f) + ((c & 2) ? dz[1] : 0.0f) + ((c & 4) ? dz[2] : 0.0f);
+        zmin = fminf(zmin, cz[c]);
+    }
+    const float zl = zmin - eps;
+    if (!(zl > 0.0f)) return true;   // a corner at or behind the camera plane (or a NaN)
+    float umin = 3e38f, umax = -3e38f, vmin = 3e38f, vmax = -3e38f, mag = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const float rz = gs2m_fast_rcp(cz[c]);                      // 1 ulp: within rnd below
+        const float u = cx[c] * f0.fx_f * rz, v = cy[c] * f0.fy_f * rz;   // relative to the principal point
+        umin = fminf(umin, u);
+        umax = fmaxf(umax, u);
+        vmin = fminf(vmin, v);
+        vmax = fmaxf(vmax, v);
+        mag += fabsf(u) + fabsf(v);   // fminf / fmaxf drop a NaN: this keeps it
+    }
+    if (!(mag < 1e9f)) return true;
+    const float au = fmaxf(fabsf(umin), fabsf(umax)), av = fmaxf(fabsf(vmin), fabsf(vmax));
+    const float k = eps / zl, rnd = 1.0f / 1048576.0f;
+    const float mu = 1.0f + k * (fabsf(f0.fx_f) + au) + rnd * (au + fabsf(f0.cx_f) + 1.0f);
+    const float mv = 1.0f + k * (fabsf(f0.fy_f) + av) + rnd * (av + fabsf(f0.cy_f) + 1.0f);
+    if (!(mu < 1e6f && mv < 1e6f)) return true;
+    const float x0 = fmaxf(floorf(umin + f0.cx_f - mu), 0.0f), x1 = fminf(ceilf(umax + f0.cx_f + mu), (float)(f0.W - 1));
+    const float y0 = fmaxf(floorf(vmin + f0.cy_f - mv), 0.0f), y1 = fminf(ceilf(vmax + f0.cy_f + mv), (float)(f0.H - 1));
+    if (x0 > x1 || y0 > y1) return false;   // no voxel sees a pixel.  Otherwise 0 <= x0 <= x1 < W and 0 <= y0 <= y1 < H
+    const int tx0 = (int)x0 / GS2M_TSDF_TILE, tx1 = (int)x1 / GS2M_TSDF_TILE, ty0 = (int)y0 / GS2M_TSDF_TILE, ty1 = (int)y1 / GS2M_TSDF_TILE;
+    if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) > GS2M_TSDF_CULL_MAX_TILES) return true;   // a camera this close: not worth the reads
+    // 4 x 4 tiles per round trip: a tile past the footprint's edge reads the edge tile again (harmless to a maximum), so the
+    // 16 loads are unconditional and go out together.  A micro-column's footprint is 2-4 tiles wide and up to 9 long.
+    float dmax = 0.0f;
+    for (int ty = ty0; ty <= ty1; ty += 4) {
+        for (int tx = tx0; tx <= tx1; tx += 4) {
+            float d[16];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float* __restrict__ row = tiles + (size_t)(ty + i < ty1 ? ty + i : ty1) * tiles_x;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d[4 * i + j] = row[tx + j < tx1 ? tx + j : tx1];
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (d[i] > dmax) dmax = d[i];
+        }
+    }
+    if (!(dmax > 0.0f)) return false;   // no depth sample in the footprint
+    const float zlow = zl - vl;
+    return !(dmax - zlow <= -f0.sdf_trunc_f);
+}
+
+GS2M_KERNEL void __launch_bounds__(256)
+k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames, const float* __restrict__ tiles) {
     __shared__ float s_p0[16], s_p1[16];
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -473,17 +640,30 @@ k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) 
         float* bt = V.tsdf + (size_t)slot * GS2M_TSDF_VOX;
         float* bw = V.weight + (size_t)slot * GS2M_TSDF_VOX;
         unsigned* bc = V.rgb + (size_t)slot * 3 * GS2M_TSDF_VOX;
+        // The cull: lane f tests frame f of the batch (at most 64 of either) for THIS wave's micro-column, and the wave walks
+        // only the frames the test could not prove dead.  The frame loop has no workgroup barrier, so the four waves may walk
+        // different frame sets; a wave left without a frame skips its state loads and stores as well.
+        bool live = false;
+        if ((fm >> lane) & 1ull) {
+            const int tiles_x = GS2M_TSDF_TILES(f0.W), tiles_y = GS2M_TSDF_TILES(f0.H);
+            live = tsdf_pass_live(f0, reinterpret_cast<const float4*>(frames[lane].f.E), tiles + (size_t)lane * tiles_y * tiles_x, tiles_x,
+                                  s_p0[4 * xq], s_p0[4 * xq + 3], s_p1[4 * wave], s_p1[4 * wave + 3], p2);
+        }
+        const unsigned long long fm_live = fm & gs2m_ballot(live ? 1 : 0);
         float w[4], t[4];
         unsigned c0[4], c1[4], c2[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            w[j] = bw[vi0 + VS * j];
-            t[j] = bt[vi0 + VS * j];
+            w[j] = t[j] = 0.0f;
             c0[j] = c1[j] = c2[j] = 0u;
-            if (V.has_color) {
-                c0[j] = bc[vi0 + VS * j];
-                c1[j] = bc[GS2M_TSDF_VOX + vi0 + VS * j];
-                c2[j] = bc[2 * GS2M_TSDF_VOX + vi0 + VS * j];
+            if (fm_live != 0ull) {
+                w[j] = bw[vi0 + VS * j];
+                t[j] = bt[vi0 + VS * j];
+                if (V.has_color) {
+                    c0[j] = bc[vi0 + VS * j];
+                    c1[j] = bc[GS2M_TSDF_VOX + vi0 + VS * j];
+                    c2[j] = bc[2 * GS2M_TSDF_VOX + vi0 + VS * j];
+                }
             }
         }
         // Software pipeline over the frames of the block: the projection of frame n + 1 and its depth gathers are issued
@@ -564,7 +744,7 @@ k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) 
                 }
             }
         };
-        unsigned long long todo = fm;
+        unsigned long long todo = fm_live;
         Probe A, B;
         if (todo != 0ull) {
             probe(__ffsll(todo) - 1, A);   // frames in ascending order
@@ -586,6 +766,7 @@ k_tsdf_integrate_batch(TsdfVolume V, const TsdfBatchFrame* __restrict__ frames) 
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
+            if (fm_live == 0ull) continue;   // nothing loaded, nothing changed
             bw[vi0 + VS * j] = w[j];
             bt[vi0 + VS * j] = t[j];
             if (V.has_color) {

@@ -16,13 +16,17 @@ void gs2m_launch_tsdf_integrate(hipStream_t st, int n_wg, const TsdfVolume& V, c
     GS2M_LAUNCH(k_tsdf_integrate, dim3(n_wg), dim3(256), 0, st, V, f, depth, color, mask);
 }
 void gs2m_launch_tsdf_touch_batch(hipStream_t st, const TsdfVolume& V, const TsdfFrame& f, int n_frames,
-                                  const TsdfBatchFrame* frames) {
+                                  const TsdfBatchFrame* frames, float* tiles) {
     const int n = f.nx * f.ny;
-    GS2M_LAUNCH(k_tsdf_touch_batch, dim3((n + 255) / 256, n_frames), dim3(256), 0, st, V, frames);
+    // the sweep's max-depth map, tiles[n_frames][tiles_y][tiles_x], in the same launch: a workgroup per 1024 columns x 8 rows
+    const int tiles_x = GS2M_TSDF_TILES(f.W), tiles_y = GS2M_TSDF_TILES(f.H);
+    const unsigned n_touch = (unsigned)((n + 255) / 256), map_wg_x = (unsigned)((f.W + 1023) / 1024);
+    GS2M_LAUNCH(k_tsdf_touch_batch, dim3(n_touch + map_wg_x * (unsigned)tiles_y, n_frames), dim3(256), 0, st, V, frames, n_touch, tiles, tiles_x,
+                tiles_y, map_wg_x);
     GS2M_LAUNCH(k_tsdf_compact, dim3((V.hash_cap + 1023u) / 1024u), dim3(1024), 0, st, V, 0u);
 }
-void gs2m_launch_tsdf_integrate_batch(hipStream_t st, int n_cu, const TsdfVolume& V, const TsdfBatchFrame* frames) {
-    GS2M_LAUNCH(k_tsdf_integrate_batch, dim3(n_cu * 6), dim3(256), 0, st, V, frames);
+void gs2m_launch_tsdf_integrate_batch(hipStream_t st, int n_cu, const TsdfVolume& V, const TsdfBatchFrame* frames, const float* tiles) {
+    GS2M_LAUNCH(k_tsdf_integrate_batch, dim3(n_cu * 6), dim3(256), 0, st, V, frames, tiles);
     GS2M_LAUNCH(k_tsdf_clear_fmask, dim3(16), dim3(256), 0, st, V);
 }
 void gs2m_launch_tsdf_clear_used(hipStream_t st, const TsdfVolume& V) {
