@@ -460,15 +460,17 @@ extern "C" int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const
 // Backward of the last gs2m_rasterize_forward on this handle: the projected records, the sorted per-tile lists and the ranges
 // are still in the arenas.  Stages: row offsets (scan of the rect areas) -> clear the row buffer -> compositing backward (one row
 // per instance, plain stores) -> per-Gaussian backward (sums the rows, continues to the inputs).
-extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int R, const float* background, int width,
-                                       int height, const float* means3D, const float* shs, const float* colors_precomp,
-                                       const float* scales, float scale_modifier, const float* rotations,
-                                       const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                                       const float* cam_pos, float tan_fovx, float tan_fovy, const float* dL_dpix,
-                                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                                       int debug, gs2m_stream stream) {
-    (void)R;   // the instance count is part of the handle's state
+// Body of gs2m_rasterize_backward (depth = 0: the colour kernels, dL_dpix required) and gs2m_rasterize_backward_depth (depth = 1:
+// the instantiations with the depth / opacity map terms, every upstream map may be null).
+static int rasterize_backward(gs2m_raster* r, const char* who, int depth, int P, int D, int M, const float* background, int width,
+                              int height, const float* means3D, const float* shs, const float* colors_precomp,
+                              const float* scales, float scale_modifier, const float* rotations,
+                              const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                              const float* cam_pos, float tan_fovx, float tan_fovy, const float* dL_dpix,
+                              const float* dL_ddepth_expected, const float* dL_ddepth_median, const float* dL_dalpha,
+                              float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                              int debug, gs2m_stream stream) {
     if (!r) {
         gs2m_set_error("null handle");
         return 1;
@@ -476,21 +478,21 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
     hipStream_t st = (hipStream_t)stream;
     GS2M_HIPCHK(hipSetDevice(r->device));
     if (!r->fw_valid) {
-        gs2m_set_error("gs2m_rasterize_backward: the handle holds no state of a gs2m_rasterize_forward call (the last call was "
-                       "gs2m_render_views or gs2m_raster_reserve, or none)");
+        gs2m_set_error("%s: the handle holds no state of a gs2m_rasterize_forward call (the last call was "
+                       "gs2m_render_views or gs2m_raster_reserve, or none)", who);
         return 1;
     }
     if (P != r->fw_P || width != r->fw_W || height != r->fw_H) {
-        gs2m_set_error("gs2m_rasterize_backward: P %d / %dx%d do not match the last forward (P %d / %dx%d)", P, width, height,
+        gs2m_set_error("%s: P %d / %dx%d do not match the last forward (P %d / %dx%d)", who, P, width, height,
                        r->fw_P, r->fw_W, r->fw_H);
         return 1;
     }
     if (r->fw_tile_rows != 1 || r->opt_tile_rows != 1) {
-        gs2m_set_error("gs2m_rasterize_backward needs the 16 x 16 instance lists: GS2M_OPT_TILE_ROWS 2 is not supported");
+        gs2m_set_error("%s needs the 16 x 16 instance lists: GS2M_OPT_TILE_ROWS 2 is not supported", who);
         return 1;
     }
     if (r->opt_pair_batch > 1) {
-        gs2m_set_error("gs2m_rasterize_backward is not available with GS2M_OPT_PAIR_BATCH (a gs2m_render_views option)");
+        gs2m_set_error("%s is not available with GS2M_OPT_PAIR_BATCH (a gs2m_render_views option)", who);
         return 1;
     }
     if (D < 0 || D > 3) {
@@ -498,9 +500,9 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
         return 1;
     }
     if (P == 0) return 0;   // every output is empty
-    if (!dL_dpix || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot ||
+    if ((!depth && !dL_dpix) || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot ||
         !means3D || !background || !viewmatrix || !projmatrix || !cam_pos) {
-        gs2m_set_error("gs2m_rasterize_backward: NULL required pointer");
+        gs2m_set_error("%s: NULL required pointer", who);
         return 1;
     }
     if ((shs == nullptr) == (colors_precomp == nullptr)) {
@@ -513,7 +515,7 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
         return 1;
     }
     if (shs && (M < (D + 1) * (D + 1) || !dL_dsh)) {
-        gs2m_set_error("gs2m_rasterize_backward: M = %d SH coefficients < (D+1)^2 = %d, or dL_dsh is NULL", M, (D + 1) * (D + 1));
+        gs2m_set_error("%s: M = %d SH coefficients < (D+1)^2 = %d, or dL_dsh is NULL", who, M, (D + 1) * (D + 1));
         return 1;
     }
     const int saved_debug = r->opt_debug;
@@ -536,11 +538,11 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
     GS2M_HIPCHK(hipMemcpyAsync(&n_rows, r->d_bw_total.get(), sizeof(n_rows), hipMemcpyDeviceToHost, st));
     GS2M_HIPCHK(hipStreamSynchronize(st));
     if (r->h_status.get()[1].overflow) {
-        gs2m_set_error("gs2m_rasterize_backward: the forward overflowed its instance arena (gs2m_raster_status / gs2m_raster_reserve, then run it again)");
+        gs2m_set_error("%s: the forward overflowed its instance arena (gs2m_raster_status / gs2m_raster_reserve, then run it again)", who);
         return 1;
     }
     if (n_rows > 0xfffffff0ull) {
-        gs2m_set_error("gs2m_rasterize_backward: %llu instance rows exceed the 32-bit row offsets", n_rows);
+        gs2m_set_error("%s: %llu instance rows exceed the 32-bit row offsets", who, n_rows);
         return 1;
     }
     if (r->d_bw_rows.reserve((size_t)(n_rows ? n_rows : 1ull) * GS2M_BW_ROW)) return 1;
@@ -549,7 +551,7 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
         // rows no wave writes (instances behind every pixel's last contributor, tiles a cull level dropped) must read as zero
         GS2M_HIPCHK(hipMemsetAsync(r->d_bw_rows.get(), 0, sizeof(float) * (size_t)n_rows * GS2M_BW_ROW, st));
         gs2m_launch_blend_backward(st, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, r->d_cams.get(), P, r->last_cap, dL_dpix, r->d_bw_offset.get(),
-                                   r->d_bw_rows.get(), n_rows);
+                                   r->d_bw_rows.get(), n_rows, depth, dL_ddepth_expected, dL_ddepth_median, dL_dalpha);
         if (dbg_check(r, st, "blend backward")) return 1;
     }
     GaussIn g;
@@ -578,9 +580,43 @@ extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int 
     o.dL_dsh = shs ? dL_dsh : nullptr;
     o.dL_dscale = dL_dscale;
     o.dL_drot = dL_drot;
-    gs2m_launch_gaussian_backward(st, g, r->d_cams.get(), recs, r->d_bw_offset.get(), r->d_bw_rows.get(), n_rows, o);
+    gs2m_launch_gaussian_backward(st, g, r->d_cams.get(), recs, r->d_bw_offset.get(), r->d_bw_rows.get(), n_rows, o, depth);
     if (dbg_check(r, st, "gaussian backward")) return 1;
     return 0;
+}
+
+extern "C" int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int R, const float* background, int width,
+                                       int height, const float* means3D, const float* shs, const float* colors_precomp,
+                                       const float* scales, float scale_modifier, const float* rotations,
+                                       const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                       const float* cam_pos, float tan_fovx, float tan_fovy, const float* dL_dpix,
+                                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                       int debug, gs2m_stream stream) {
+    (void)R;   // the instance count is part of the handle's state
+    return rasterize_backward(r, "gs2m_rasterize_backward", 0, P, D, M, background, width, height, means3D, shs, colors_precomp,
+                              scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
+                              tan_fovy, dL_dpix, nullptr, nullptr, nullptr, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                              dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream);
+}
+
+// The same backward with gradients through the maps of gs2m_rasterize_depth.  With the three map gradients null and dL_dpix given
+// it IS gs2m_rasterize_backward (the colour kernels: identical bits); otherwise the kernels' depth instantiations run.
+extern "C" int gs2m_rasterize_backward_depth(gs2m_raster* r, int P, int D, int M, int R, const float* background, int width,
+                                             int height, const float* means3D, const float* shs, const float* colors_precomp,
+                                             const float* scales, float scale_modifier, const float* rotations,
+                                             const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                             const float* cam_pos, float tan_fovx, float tan_fovy, const float* dL_dpix,
+                                             const float* dL_ddepth_expected, const float* dL_ddepth_median,
+                                             const float* dL_dalpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                             float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                                             float* dL_dscale, float* dL_drot, int debug, gs2m_stream stream) {
+    (void)R;
+    const int depth = (dL_ddepth_expected || dL_ddepth_median || dL_dalpha || !dL_dpix) ? 1 : 0;
+    return rasterize_backward(r, "gs2m_rasterize_backward_depth", depth, P, D, M, background, width, height, means3D, shs,
+                              colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                              tan_fovx, tan_fovy, dL_dpix, dL_ddepth_expected, dL_ddepth_median, dL_dalpha, dL_dmean2D, dL_dconic,
+                              dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream);
 }
 
 // Depth and opacity maps of the last gs2m_rasterize_forward on this handle (raster_depth.h): one kernel over the kept records,

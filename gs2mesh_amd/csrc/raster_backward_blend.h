@@ -26,6 +26,21 @@
 //     dL/do = G dL/dalpha also where the cap binds;
 //   * dL/dmean2D is accumulated in NDC-scaled units, 0.5 W and 0.5 H (:460-461);
 //   * the background term  -T_final / (1 - alpha) * (bg . dL/dpixel)  (:531-534).
+//
+// Gradients through the depth and opacity maps (k_blend_backward<WPB, true>, gs2m_rasterize_backward_depth; an extension like
+// the maps themselves).  Per pixel the forward walk of raster_depth.h gives, over the contributors j,  w_j = alpha_j T_j,
+// S = sum w_j,  Z = sum w_j z_j,  T_f,  D = S > 0 ? Z / S : 0,  A = 1 - T_f  and  med = z_m, m the first contributor after
+// which T <= 0.5.  With upstream gradients gD, gM, gA ([H,W] each, a null map = zeros):
+//   * expected depth: one more "colour channel" over a zero background whose per-instance value is u_j = (gD / S)(z_j - D)
+//     (0 where S == 0); it adds T_j (u_j - rec_j) to dL/dalpha_j, rec the same behind-the-contributor recurrence as colour's;
+//   * opacity map: dA/dalpha_j = T_f / (1 - alpha_j), the shape of the background term: bgdot becomes bgdot - gA;
+//   * dL/dz_j, the tenth value of the instance row (row[9]): every contributing pixel adds w_j gD / S, the pixel whose median
+//     is this instance also adds gM.  med is piecewise constant in everything but z_m; that is the stated derivative.  The
+//     per-Gaussian pass adds (vm[2], vm[6], vm[10]) sum(row[9]) to dL/dmean3D: z_j is the view-space z of the centre.
+// dL/dalpha continues into mean2D, conic and opacity exactly as for colour, under the same departures.  Walk 1 accumulates S
+// and Z with k_blend_depth's operations (S += w; Z = fmaf(w, z, Z)) and records the median's list position next to n_contrib,
+// so D has the forward's bits and the median is the forward's instance.  Values nine and ten share one 2-value butterfly
+// (bw_reduce2).  The DEPTH = false instantiation is the colour backward unchanged: it neither reads nor writes row[9].
 #pragma once
 #include "raster_common.h"
 
@@ -69,15 +84,35 @@ GS2M_DEVICE float bw_reduce1(float d) {
     return d;
 }
 
+// sum over the 64 lanes of two per-lane values: afterwards every even lane holds the complete sum of a0 and every odd lane that
+// of a1 (1 + 5 shuffles).  Floating-point addition commutes, so the sum of a0 has the bits bw_reduce1(a0) gives.
+GS2M_DEVICE float bw_reduce2(const float a0, const float a1, const int lane) {
+    const bool b0 = lane & 1;
+    float d = (b0 ? a1 : a0) + gs2m_shfl_xor(b0 ? a0 : a1, 1);
+#pragma unroll
+    for (int m = 2; m < 64; m <<= 1) d += gs2m_shfl_xor(d, m);
+    return d;
+}
+
+// upstream gradients of the depth and opacity maps (raster_depth.h), [H,W] each; a null map is a map of zeros
+struct BwDepthGrads {
+    const float* dL_ddepth;    // expected depth D = Z / S
+    const float* dL_dmedian;   // median depth
+    const float* dL_dalpha;    // accumulated opacity A = 1 - T_final
+};
+
 // grid: ceil(tiles / WPB) workgroups of WPB waves; wave w of workgroup b composites tile b * WPB + w of the (single) view.
-template <int WPB>
+// DEPTH = false is the colour backward (gs2m_rasterize_backward): dg is not read and row value 9 is not written.
+template <int WPB, bool DEPTH>
 GS2M_KERNEL void __launch_bounds__(64 * WPB)
 k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ tile_start, const GeomRecs recs,
                  const CamUniform* __restrict__ cams, int P, unsigned cap, const float* __restrict__ dL_dpix,
-                 const unsigned* __restrict__ row_offset, float* __restrict__ rows, unsigned long long n_rows) {
-    // staged instance: a = {mx, my, ca, cb}, b = {cc, op, r, g}, c = {b, row index (bits)}
+                 const unsigned* __restrict__ row_offset, float* __restrict__ rows, unsigned long long n_rows,
+                 const BwDepthGrads dg) {
+    // staged instance: a = {mx, my, ca, cb}, b = {cc, op, r, g}, c = {b, row index (bits)}; DEPTH: z = view-space depth
     __shared__ float4 s_a[WPB][64], s_b[WPB][64];
     __shared__ float2 s_c[WPB][64];
+    __shared__ float s_z[DEPTH ? WPB : 1][64];
     const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
     const CamUniform& cam = cams[0];
     const int W = cam.W, H = cam.H, gx = cam.gx;
@@ -88,6 +123,7 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
     float4* sa = &s_a[wave][0];
     float4* sb = &s_b[wave][0];
     float2* sc = &s_c[wave][0];
+    float* sz = &s_z[DEPTH ? wave : 0][0];
     unsigned r0 = tile_start[tile], r1 = tile_start[tile + 1];
     if (r0 > cap) r0 = cap;
     if (r1 > cap) r1 = cap;
@@ -99,6 +135,10 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
     float pxf[4], pyf[4], T[4], dp0[4], dp1[4], dp2[4];
     int ncontrib[4];     // list position (relative to r0) after the pixel's last contributor
     bool done[4];
+    // DEPTH: walk 1 carries S, Z and the list position after the median contributor (0: none); walk 2 keeps gD / S in sS and
+    // D in sZ
+    float sS[4], sZ[4], gM[4];
+    int medpos[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);
@@ -109,9 +149,18 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
         ncontrib[k] = 0;
         done[k] = !inside;
         const size_t pix = (size_t)y * W + x;
-        dp0[k] = inside ? dL_dpix[pix] : 0.0f;
-        dp1[k] = inside ? dL_dpix[plane + pix] : 0.0f;
-        dp2[k] = inside ? dL_dpix[2 * plane + pix] : 0.0f;
+        if constexpr (DEPTH) {
+            const bool col = inside && dL_dpix != nullptr;
+            dp0[k] = col ? dL_dpix[pix] : 0.0f;
+            dp1[k] = col ? dL_dpix[plane + pix] : 0.0f;
+            dp2[k] = col ? dL_dpix[2 * plane + pix] : 0.0f;
+            sS[k] = sZ[k] = 0.0f;
+            medpos[k] = 0;
+        } else {
+            dp0[k] = inside ? dL_dpix[pix] : 0.0f;
+            dp1[k] = inside ? dL_dpix[plane + pix] : 0.0f;
+            dp2[k] = inside ? dL_dpix[2 * plane + pix] : 0.0f;
+        }
     }
     // the 64 instances [base, base + 64) of the list -> LDS (lane l stages instance base + l)
     auto stage = [&](const unsigned base) __attribute__((always_inline)) {
@@ -132,6 +181,7 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
             c.x = rc.x;
             c.y = __uint_as_float(row);
             sc[lane] = c;
+            if constexpr (DEPTH) sz[lane] = rc.y;
         }
         gs2m_wave_sync();
     };
@@ -142,6 +192,8 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
         const int nb = (int)(r1 - base) < 64 ? (int)(r1 - base) : 64;
         for (int j = 0; j < nb; ++j) {
             const float4 A = sa[j], B = sb[j];
+            float z = 0.0f;
+            if constexpr (DEPTH) z = sz[j];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float dx, dy, G, alpha;
@@ -150,6 +202,12 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
                 const bool sat = ok && test_T < 0.0001f;     // stop BEFORE accumulating (forward.cu:345-350)
                 done[k] = done[k] || sat;
                 if (ok && !sat) {
+                    if constexpr (DEPTH) {   // k_blend_depth's own operations: D below has the forward's bits
+                        const float w = alpha * T[k];
+                        sS[k] += w;
+                        sZ[k] = fmaf(w, z, sZ[k]);
+                        if (medpos[k] == 0 && test_T <= 0.5f) medpos[k] = (int)(base - r0) + j + 1;
+                    }
                     T[k] = test_T;
                     ncontrib[k] = (int)(base - r0) + j + 1;
                 }
@@ -176,6 +234,25 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
         lc0[k] = lc1[k] = lc2[k] = 0.0f;
         ar0[k] = ar1[k] = ar2[k] = 0.0f;
     }
+    // DEPTH: the expected depth is one more channel of value u_j = (gD / S) (z_j - D) over a zero background, the opacity map
+    // has the background term's shape:  dA/dalpha_j = T_final / (1 - alpha_j)
+    float lu[4], aru[4];
+    if constexpr (DEPTH) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // a pixel with a contributor lies inside the image and has S > 0 (alpha >= 1/255, T >= 1e-4); the others add nothing
+            const bool live = ncontrib[k] > 0;
+            const size_t pix = (size_t)(py0 + 8 * (k >> 1)) * W + (size_t)(px0 + 8 * (k & 1));
+            const float S = sS[k];
+            const float gD = (live && dg.dL_ddepth) ? dg.dL_ddepth[pix] : 0.0f;
+            gM[k] = (live && dg.dL_dmedian) ? dg.dL_dmedian[pix] : 0.0f;
+            const float gA = (live && dg.dL_dalpha) ? dg.dL_dalpha[pix] : 0.0f;
+            sZ[k] = S > 0.0f ? sZ[k] / S : 0.0f;
+            sS[k] = S > 0.0f ? gD / S : 0.0f;
+            bgdot[k] -= gA;
+            lu[k] = aru[k] = 0.0f;
+        }
+    }
     const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;   // pixel per NDC unit (backward.cu:460-461)
     for (int bi = (nmax - 1) / 64; bi >= 0; --bi) {
         const unsigned base = r0 + 64u * (unsigned)bi;
@@ -185,7 +262,9 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
             const int idx = 64 * bi + j;
             const float4 A = sa[j], B = sb[j];
             const float2 Cc = sc[j];
-            float acc[8], acc8 = 0.0f;   // mx my ca cb cc op r g | b
+            float acc[8], acc8 = 0.0f, acc9 = 0.0f;   // mx my ca cb cc op r g | b | z (DEPTH)
+            float z = 0.0f;
+            if constexpr (DEPTH) z = sz[j];
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[i] = 0.0f;
             bool any = false;
@@ -205,6 +284,13 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
                     lc1[k] = B.w;
                     lc2[k] = Cc.x;
                     float dL_dalpha = (B.z - ar0[k]) * dp0[k] + (B.w - ar1[k]) * dp1[k] + (Cc.x - ar2[k]) * dp2[k];
+                    if constexpr (DEPTH) {
+                        const float u = sS[k] * (z - sZ[k]);
+                        aru[k] = last_alpha[k] * lu[k] + (1.0f - last_alpha[k]) * aru[k];
+                        lu[k] = u;
+                        dL_dalpha += u - aru[k];
+                        acc9 += w * sS[k] + (idx + 1 == medpos[k] ? gM[k] : 0.0f);
+                    }
                     dL_dalpha *= T[k];
                     last_alpha[k] = alpha;
                     dL_dalpha += (-Tf[k] / (1.0f - alpha)) * bgdot[k];   // background term (backward.cu:531-534)
@@ -223,13 +309,15 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
             }
             if (gs2m_ballot_b(any) == 0ull) continue;   // no lane contributed: the row keeps its zeros
             const float s = bw_reduce8(acc, lane);
-            const float s8 = bw_reduce1(acc8);
+            float s8;
+            if constexpr (DEPTH) s8 = bw_reduce2(acc8, acc9, lane);
+            else s8 = bw_reduce1(acc8);
             const unsigned long long row = (unsigned long long)__float_as_uint(Cc.y);
             if (row < n_rows) {
                 float* dst = rows + (size_t)row * GS2M_BW_ROW;
                 // lane l < 8 holds value 4 (l & 1) + 2 ((l >> 1) & 1) + ((l >> 2) & 1); lane 8 stores the ninth
                 if (lane < 8) dst[4 * (lane & 1) + 2 * ((lane >> 1) & 1) + ((lane >> 2) & 1)] = s;
-                else if (lane == 8) dst[8] = s8;
+                else if (lane == 8 || (DEPTH && lane == 9)) dst[lane] = s8;   // lane 9 (odd) holds the tenth value
             }
         }
     }

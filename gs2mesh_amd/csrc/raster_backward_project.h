@@ -15,6 +15,7 @@
 //   * x_grad_mul / y_grad_mul: no gradient to t.x / t.y where the forward clamped them to the 1.3 tan(fov) frustum (:175-176);
 //   * clamped SH channels (colour < 0 -> 0) pass no gradient (:32-34);
 //   * dL/dmean2D stays in the NDC-scaled units the compositing accumulated, as [P,3] with z = 0 (:460-461).
+// The gradients through the depth maps enter here as dL/dalpha already folded into the first nine row values, plus row[9].
 // One difference FROM the reference: dL/dscale carries the factor scale_modifier (the true derivative of Sigma = R (mod s)^2 R^T);
 // the reference's computeCov3D omits it (:321-325).  Identical at scale_modifier = 1, the only value training uses.
 #pragma once
@@ -140,6 +141,9 @@ GS2M_DEVICE void bw_sh_basis(int deg, float x, float y, float z, float* b, float
     by[15] = 6.0f * c30 * xy;
 }
 
+// DEPTH: the rows carry dL/dz of the centre's view-space depth as their tenth value (gs2m_rasterize_backward_depth,
+// raster_backward_blend.h); its sum times the view matrix's z row is added to dL/dmean3D.  DEPTH = false never reads that value.
+template <bool DEPTH>
 GS2M_KERNEL void __launch_bounds__(256)
 k_gaussian_backward(GaussIn g, const CamUniform* __restrict__ cams, GeomRecs recs, const unsigned* __restrict__ row_offset,
                     const float* __restrict__ rows, unsigned long long n_rows, BwOut o) {
@@ -172,6 +176,7 @@ k_gaussian_backward(GaussIn g, const CamUniform* __restrict__ cams, GeomRecs rec
     float acc[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) acc[k] = 0.0f;
+    float accz = 0.0f;
     if (pv.ok) {
         // ---- the Gaussian's instance rows, in slot order
         const unsigned n = bw_rect_area(recs.c[i]);
@@ -189,6 +194,7 @@ k_gaussian_backward(GaussIn g, const CamUniform* __restrict__ cams, GeomRecs rec
             acc[6] += b.z;
             acc[7] += b.w;
             acc[8] += c;
+            if constexpr (DEPTH) accz += r4[2].y;
         }
         // ---- conic -> cov2D -> cov3D and mean (backward.cu:144-274).  T = W J as in cov2d_ewa (raster_math.h): rows
         // T0 = (T00, T01, T02), T1 = (T10, T11, T12); a = T0 V T0^T + 0.3, b = T0 V T1^T, c = T1 V T1^T + 0.3
@@ -250,6 +256,11 @@ k_gaussian_backward(GaussIn g, const CamUniform* __restrict__ cams, GeomRecs rec
             dmean[0] += (pm[0] * m_w - pm[3] * mul1) * gx2 + (pm[1] * m_w - pm[3] * mul2) * gy2;
             dmean[1] += (pm[4] * m_w - pm[7] * mul1) * gx2 + (pm[5] * m_w - pm[7] * mul2) * gy2;
             dmean[2] += (pm[8] * m_w - pm[11] * mul1) * gx2 + (pm[9] * m_w - pm[11] * mul2) * gy2;
+        }
+        if constexpr (DEPTH) {   // z = vm[2] x + vm[6] y + vm[10] z + vm[14] (the record's depth)
+            dmean[0] += vm[2] * accz;
+            dmean[1] += vm[6] * accz;
+            dmean[2] += vm[10] * accz;
         }
     }
     // ---- colour -> SH coefficients and view direction (backward.cu:20-139)

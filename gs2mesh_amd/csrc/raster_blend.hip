@@ -51,10 +51,16 @@ int gs2m_launch_blend(hipStream_t st, int variant, int tile_rows, int nv, int gx
 // backward of the compositing (one view, 16 x 16 lists): one wave per tile, four tiles per workgroup
 void gs2m_launch_blend_backward(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
                                 GeomRecs recs, const CamUniform* cams, int P, unsigned cap, const float* dL_dpix,
-                                const unsigned* row_offset, float* rows, unsigned long long n_rows) {
+                                const unsigned* row_offset, float* rows, unsigned long long n_rows, int depth,
+                                const float* dL_ddepth, const float* dL_dmedian, const float* dL_dalpha) {
     const int tiles = gx * gy;
-    GS2M_LAUNCH((k_blend_backward<4>), dim3((tiles + 3) / 4), dim3(256), 0, st, keys, tile_start, recs, cams, P, cap, dL_dpix,
-                row_offset, rows, n_rows);
+    const BwDepthGrads dg{dL_ddepth, dL_dmedian, dL_dalpha};
+    if (depth)
+        GS2M_LAUNCH((k_blend_backward<4, true>), dim3((tiles + 3) / 4), dim3(256), 0, st, keys, tile_start, recs, cams, P, cap,
+                    dL_dpix, row_offset, rows, n_rows, dg);
+    else
+        GS2M_LAUNCH((k_blend_backward<4, false>), dim3((tiles + 3) / 4), dim3(256), 0, st, keys, tile_start, recs, cams, P, cap,
+                    dL_dpix, row_offset, rows, n_rows, dg);
 }
 
 // depth / opacity maps of the last single-view forward (16 x 16 lists): one wave per tile, four tiles per workgroup

@@ -16,6 +16,9 @@
 // pixel's ray with anything.  A pixel without a contributor holds exactly 0 in all three maps; z > 0.2 for every listed
 // Gaussian (the near cull), so 0 means "no depth".  1 - T is exact for T in [0.5, 1]: depth_median > 0 exactly where alpha >= 0.5.
 //
+// Gradients through these maps: k_blend_backward<WPB, true> (raster_backward_blend.h), which repeats this walk's S and Z operation
+// for operation.
+//
 // No atomics, plain stores: every pixel of the image is written exactly once by the lane that owns it, the pixels of tiles with
 // an empty list included.
 #pragma once

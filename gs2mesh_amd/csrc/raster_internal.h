@@ -57,11 +57,16 @@ struct BwOut {
 // block_sum = scratch of ceil(P / 256) words
 void gs2m_launch_bw_row_offsets(hipStream_t st, GeomRecs recs, int P, unsigned* block_sum, unsigned* row_offset,
                                 unsigned long long* total_rows);
+// depth = 0: the colour backward (dL_dpix required, the three map gradients not read, row value 9 neither written nor read);
+// depth = 1: the instantiations with the depth / opacity map terms (gs2m_rasterize_backward_depth): dL_dpix and each of
+// dL_ddepth / dL_dmedian / dL_dalpha ([H,W]) may be null = zeros.  Both launches of one backward take the same flag.
 void gs2m_launch_blend_backward(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
                                 GeomRecs recs, const CamUniform* cams, int P, unsigned cap, const float* dL_dpix,
-                                const unsigned* row_offset, float* rows, unsigned long long n_rows);
+                                const unsigned* row_offset, float* rows, unsigned long long n_rows, int depth,
+                                const float* dL_ddepth, const float* dL_dmedian, const float* dL_dalpha);
 void gs2m_launch_gaussian_backward(hipStream_t st, const GaussIn& g, const CamUniform* cams, GeomRecs recs,
-                                   const unsigned* row_offset, const float* rows, unsigned long long n_rows, const BwOut& out);
+                                   const unsigned* row_offset, const float* rows, unsigned long long n_rows, const BwOut& out,
+                                   int depth);
 
 // ---- depth / opacity maps (gs2m_rasterize_depth): [H,W] f32 each, any of them null
 void gs2m_launch_blend_depth(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,

@@ -136,6 +136,10 @@ void gs2m_launch_bw_row_offsets(hipStream_t st, GeomRecs recs, int P, unsigned* 
 }
 
 void gs2m_launch_gaussian_backward(hipStream_t st, const GaussIn& g, const CamUniform* cams, GeomRecs recs,
-                                   const unsigned* row_offset, const float* rows, unsigned long long n_rows, const BwOut& out) {
-    GS2M_LAUNCH(k_gaussian_backward, dim3((g.P + 255) / 256), dim3(256), 0, st, g, cams, recs, row_offset, rows, n_rows, out);
+                                   const unsigned* row_offset, const float* rows, unsigned long long n_rows, const BwOut& out,
+                                   int depth) {
+    if (depth)
+        GS2M_LAUNCH((k_gaussian_backward<true>), dim3((g.P + 255) / 256), dim3(256), 0, st, g, cams, recs, row_offset, rows, n_rows, out);
+    else
+        GS2M_LAUNCH((k_gaussian_backward<false>), dim3((g.P + 255) / 256), dim3(256), 0, st, g, cams, recs, row_offset, rows, n_rows, out);
 }

@@ -18,6 +18,12 @@ colors_precomp, opacities, scales, rotations and cov3D_precomp with the referenc
 The forward state the backward needs stays in the per-device handle; if another forward ran on the handle in between, the
 backward first replays its own forward into a scratch image, so correctness never depends on call order.
 All tensors must be float32, contiguous and on the HIP device; outputs are freshly allocated.
+
+Extension (the reference renders colour only): ``GaussianRasterizer.forward(..., return_depth=True)`` returns
+``(color, radii, expected, median, alpha)`` -- the depth and opacity maps of ``gs2m_rasterize_depth`` -- and, when gradients are
+wanted, goes through ``_RasterizeGaussiansDepth``, whose backward hands the upstream gradients of the image and of the three
+maps to ONE ``gs2m_rasterize_backward_depth`` call: a depth-supervised or depth-regularised loss trains the splat.  The keyword
+defaults to False and the reference's 2-tuple is untouched.
 """
 from __future__ import annotations
 
@@ -164,6 +170,58 @@ class _RasterizeGaussians(torch.autograd.Function):
                 g["rot"] if given(rotations) else None, g["cov3D"] if given(cov3Ds_precomp) else None, None)
 
 
+def _backward_args(ctx):
+    rs = ctx.raster_settings
+    colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities = ctx.saved_tensors
+    args = dict(shs=_none_if_empty(sh), colors_precomp=_none_if_empty(colors_precomp), scales=_none_if_empty(scales),
+                rotations=_none_if_empty(rotations), cov3D_precomp=_none_if_empty(cov3Ds_precomp), sh_degree=int(rs.sh_degree),
+                scale_modifier=float(rs.scale_modifier), debug=bool(rs.debug))
+    cam = (_f32c(rs.viewmatrix), _f32c(rs.projmatrix), _f32c(rs.campos), _f32c(rs.bg), int(rs.image_width),
+           int(rs.image_height), float(rs.tanfovx), float(rs.tanfovy))
+    return args, cam
+
+
+class _RasterizeGaussiansDepth(torch.autograd.Function):
+    """``_RasterizeGaussians`` with the depth and opacity maps as three more differentiable outputs (an extension).  The
+    backward passes the four upstream gradients to one ``Rasterizer.backward`` call (``gs2m_rasterize_backward_depth``); an
+    output the loss does not use arrives as None and is passed as a NULL map.  It replays its forward when the handle's state
+    has moved on, exactly as the colour Function does."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        color, radii = _rasterize_no_grad(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                          raster_settings)
+        h = _handle(means3D.device)
+        maps = h.depth_maps(int(raster_settings.image_width), int(raster_settings.image_height), like=color)
+        ctx.raster_settings = raster_settings
+        ctx.handle = h
+        ctx.state_calls = h.state_calls
+        ctx.opacity_shape = tuple(opacities.shape)
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, maps["expected"], maps["median"], maps["alpha"]
+
+    @staticmethod
+    def backward(ctx, grad_color, _, grad_expected, grad_median, grad_alpha):
+        rs = ctx.raster_settings
+        h = ctx.handle
+        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities = ctx.saved_tensors
+        args, cam = _backward_args(ctx)
+        if h.state_calls != ctx.state_calls:
+            h.forward(_f32c(means3D), _f32c(opacities).reshape(-1), *cam, prefiltered=bool(rs.prefiltered), **args)
+            ctx.state_calls = h.state_calls
+        opt = lambda t: None if t is None else _f32c(t)
+        if grad_color is None and grad_expected is None and grad_median is None and grad_alpha is None:
+            grad_color = torch.zeros((3, cam[5], cam[4]), dtype=torch.float32, device=means3D.device)
+        g = h.backward(opt(grad_color), _f32c(means3D), *cam, grad_depth=opt(grad_expected), grad_median=opt(grad_median),
+                       grad_alpha=opt(grad_alpha), **args)
+        given = lambda t: t is not None and t.numel() > 0
+        return (g["mean3D"], g["mean2D"], g["sh"] if given(sh) else None, g["color"] if given(colors_precomp) else None,
+                g["opacity"].reshape(ctx.opacity_shape), g["scale"] if given(scales) else None,
+                g["rot"] if given(rotations) else None, g["cov3D"] if given(cov3Ds_precomp) else None, None)
+
+
 class GaussianRasterizer(nn.Module):
     """DGR/diff_gaussian_rasterization/__init__.py:171-220."""
 
@@ -181,7 +239,9 @@ class GaussianRasterizer(nn.Module):
         return present.to(torch.bool)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, return_depth=False):
+        """``return_depth=True`` (an extension; the reference returns ``(color, radii)``): ``(color, radii, expected, median,
+        alpha)`` with the [H,W] maps of ``depth_maps``, carrying the graph when gradients are wanted."""
         raster_settings = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -199,6 +259,19 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = torch.Tensor([])
         # Invoke the HIP rasterization routine
+        if return_depth:
+            tensors = (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)
+            if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
+                out = _RasterizeGaussiansDepth.apply(*tensors, raster_settings)
+                h = _handle(means3D.device)
+                self._last = (h, h.state_calls, tensors[:1] + tensors[2:])
+                return out
+            color, radii = _rasterize_no_grad(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                              raster_settings)
+            h = _handle(means3D.device)
+            self._last = (h, h.state_calls, tensors[:1] + tensors[2:])
+            maps = self.depth_maps()
+            return color, radii, maps["expected"], maps["median"], maps["alpha"]
         out = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                   cov3D_precomp, raster_settings)
         h = _handle(means3D.device)
@@ -210,7 +283,8 @@ class GaussianRasterizer(nn.Module):
         tensors -- ``expected`` (alpha-weighted mean view-space z of the contributing Gaussians' centres), ``median`` (z of the
         contributor that takes the transmittance to 0.5 or below) and ``alpha`` (accumulated opacity); 0 = no contributor
         (``gs2m_rasterize_depth``).  If another forward ran on the device's handle since, this one is replayed first into a
-        scratch image, the way the backward pass does.  The results are DETACHED: no gradient flows through depth or alpha."""
+        scratch image, the way the backward pass does.  The results are DETACHED; maps that carry the graph come from
+        ``forward(..., return_depth=True)``."""
         if self._last is None:
             raise RuntimeError("GaussianRasterizer.depth_maps: this rasteriser has not run a forward")
         h, calls, inputs = self._last

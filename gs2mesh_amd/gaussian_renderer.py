@@ -17,12 +17,14 @@ def _dev(x, device):
     return torch.as_tensor(x, dtype=torch.float32, device=device).contiguous()
 
 
-def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, return_depth=False):
+def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, return_depth=False,
+           depth_grad=False):
     """Background tensor (bg_color) must be on the GPU, as in the reference.  ``return_depth=True`` (an extension: the reference
-    renders colour only) adds three detached [H,W] maps of the same forward to the dict: ``depth`` (alpha-weighted mean
+    renders colour only) adds three [H,W] maps of the same forward to the dict: ``depth`` (alpha-weighted mean
     view-space z of the contributing Gaussians' centres), ``median_depth`` (z of the contributor that takes the transmittance
-    to one half) and ``alpha`` (accumulated opacity; render = C + (1 - alpha) * bg); 0 = no contributor.  No gradient flows
-    through them."""
+    to one half) and ``alpha`` (accumulated opacity; render = C + (1 - alpha) * bg); 0 = no contributor.  They are detached
+    unless ``depth_grad=True``: then, where gradients are wanted, they carry the graph (``gs2m_rasterize_backward_depth``) and
+    a loss on them trains the splat; ``viewspace_points.grad`` then includes their screen-space term."""
     device = pc.get_xyz.device
     tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
     tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
@@ -65,13 +67,19 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         screenspace_points.retain_grad()
     else:
         screenspace_points = torch.zeros_like(means3D)
+    inputs = dict(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
+                  scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+    maps = None
     with torch.enable_grad() if want_grad else torch.no_grad():
-        rendered_image, radii = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs,
-                                           colors_precomp=colors_precomp, opacities=opacity, scales=scales,
-                                           rotations=rotations, cov3D_precomp=cov3D_precomp)
+        if return_depth and depth_grad and want_grad:   # the maps are outputs of the autograd Function: they carry the graph
+            rendered_image, radii, expected, median, alpha = rasterizer(**inputs, return_depth=True)
+            maps = {"expected": expected, "median": median, "alpha": alpha}
+        else:
+            rendered_image, radii = rasterizer(**inputs)
     out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
            "radii": radii}
     if return_depth:
-        maps = rasterizer.depth_maps()
+        if maps is None:
+            maps = rasterizer.depth_maps()
         out.update(depth=maps["expected"], median_depth=maps["median"], alpha=maps["alpha"])
     return out

@@ -206,10 +206,12 @@ class Rasterizer:
 
     def backward(self, dL_dpix, means3D, viewmatrix, projmatrix, campos, bg, W, H, tanfovx, tanfovy, shs=None,
                  colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, sh_degree=3, scale_modifier=1.0,
-                 debug=False, want_conic=False, stream=None):
+                 debug=False, want_conic=False, stream=None, grad_depth=None, grad_median=None, grad_alpha=None):
         """``gs2m_rasterize_backward``: gradients of the LAST ``forward`` on this handle, which must have been called with
         the same inputs (``state_calls`` tells whether another ``forward`` / ``render_views`` ran since).  ``dL_dpix``
-        [3,H,W].  Returns a dict of freshly allocated arrays: mean2D[P,3] (NDC-scaled, z = 0), opacity[P], color[P,3],
+        [3,H,W].  ``grad_depth`` / ``grad_median`` / ``grad_alpha``: [H,W] upstream gradients of the ``depth_maps`` of that
+        forward (``expected``, ``median``, ``alpha``); with any of them given the call is ``gs2m_rasterize_backward_depth``,
+        a missing one counts as zeros and ``dL_dpix`` may be None as well.  Returns a dict of freshly allocated arrays: mean2D[P,3] (NDC-scaled, z = 0), opacity[P], color[P,3],
         mean3D[P,3], cov3D[P,6], sh[P,M,3] (None with ``colors_precomp``), scale[P,3], rot[P,4], and conic[P,4] with
         ``want_conic``.  Every array is written in full; synchronises the stream once."""
         P = int(means3D.shape[0])
@@ -224,13 +226,19 @@ class Rasterizer:
                  rot=_empty(means3D, (P, 4), np.float32),
                  sh=_empty(means3D, (P, M, 3), np.float32) if M else None,
                  conic=_empty(means3D, (P, 4), np.float32) if want_conic else None)
-        _lib.check(self._lib.gs2m_rasterize_backward(
+        depth = not (grad_depth is None and grad_median is None and grad_alpha is None)
+        fn = self._lib.gs2m_rasterize_backward_depth if depth else self._lib.gs2m_rasterize_backward
+        ups = (_ptr(dL_dpix, f32, "dL_dpix"),)
+        if depth:
+            ups += (_ptr(grad_depth, f32, "grad_depth"), _ptr(grad_median, f32, "grad_median"),
+                    _ptr(grad_alpha, f32, "grad_alpha"))
+        _lib.check(fn(
             self._h, P, D, M, int(self.last_num_rendered or 0), _ptr(bg, f32, "bg"), int(W), int(H),
             _ptr(means3D, f32, "means3D"), _ptr(shs, f32, "shs"), _ptr(colors_precomp, f32, "colors_precomp"),
             _ptr(scales, f32, "scales"), float(scale_modifier), _ptr(rotations, f32, "rotations"),
             _ptr(cov3D_precomp, f32, "cov3D_precomp"), _ptr(viewmatrix, f32, "viewmatrix"),
             _ptr(projmatrix, f32, "projmatrix"), _ptr(campos, f32, "campos"), float(tanfovx), float(tanfovy),
-            _ptr(dL_dpix, f32, "dL_dpix"), _ptr(g["mean2D"]), _ptr(g["conic"]), _ptr(g["opacity"]), _ptr(g["color"]),
+            *ups, _ptr(g["mean2D"]), _ptr(g["conic"]), _ptr(g["opacity"]), _ptr(g["color"]),
             _ptr(g["mean3D"]), _ptr(g["cov3D"]), _ptr(g["sh"]), _ptr(g["scale"]), _ptr(g["rot"]), int(bool(debug)), st),
             self._lib)
         return g

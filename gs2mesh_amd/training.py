@@ -60,6 +60,7 @@ class OptimizationParams:
         self.rotation_lr = 0.001
         self.percent_dense = 0.01
         self.lambda_dssim = 0.2
+        self.lambda_depth = 0.0             # weight of depth_l1_loss against train(..., depth_priors=...); an extension
         self.densification_interval = 100
         self.opacity_reset_interval = 3000
         self.densify_from_iter = 500
@@ -90,6 +91,21 @@ def cameras_extent(cameras):
 def loss_fn(image, gt, lambda_dssim):
     """train.py:89-90"""
     return (1.0 - lambda_dssim) * l1_loss(image, gt) + lambda_dssim * (1.0 - ssim(image, gt))
+
+
+def depth_l1_loss(depth, alpha, prior, valid=None):
+    """Mean absolute difference between the rendered expected depth (``render(..., return_depth=True, depth_grad=True)["depth"]``)
+    and a prior depth map over ``valid & (prior > 0)``: 0 in ``prior`` means "no depth", as everywhere in the package.  The
+    rendered depth is detached nowhere, so the loss trains the splat through ``gs2m_rasterize_backward_depth``.  ``alpha`` is
+    the rendered opacity map of the same call; this loss does not weight by it (the expected depth is already normalised by
+    the accumulated weights) -- it is part of the signature so that coverage-weighted variants are drop-ins.  An empty mask
+    gives a zero that still belongs to the graph."""
+    mask = prior > 0
+    if valid is not None:
+        mask = mask & valid.to(torch.bool)
+    n = mask.sum()
+    diff = torch.where(mask, (depth - prior).abs(), torch.zeros_like(depth))
+    return diff.sum() / n.clamp_min(1).to(depth.dtype)
 
 
 # ---- the fused loss: gs2m_photo_loss_forward / _backward (gs2mesh_amd/csrc/loss_kernels.h) -----------------------------------
@@ -196,7 +212,7 @@ def fused_ssim(img1, img2, *, lib=None):
 
 
 def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False, seed=0, callback=None, timing=None,
-          loss="torch"):
+          loss="torch", depth_priors=None):
     """The loop of train.py:51-128 over ``opt.iterations`` iterations -> the loss of every iteration.
 
     ``gaussians``: a ``GaussianModel`` after ``training_setup(opt)``; ``cameras``: ``graphics.Camera`` objects; ``images``: the
@@ -208,9 +224,15 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
     ``loss``: ``"torch"`` (``loss_fn``, the default) or ``"fused"`` (``fused_loss``, the HIP kernels).  With
     ``opt.optimizer_type`` ``"fused"`` or ``"sparse_adam"`` (``gaussians.optimizer`` is then an ``optim.FusedAdam``) the
     densification statistics and the step are one kernel each, and an iteration that neither densifies nor resets opacity
-    has no host wait in its update phase; ``"sparse_adam"`` steps only the rows the view saw (``radii > 0``)."""
+    has no host wait in its update phase; ``"sparse_adam"`` steps only the rows the view saw (``radii > 0``).
+    ``depth_priors``: None, or one [H,W] depth map per camera on the device (view-space z, 0 = invalid; e.g. what ``Stereo`` or
+    ``RenderedDepth`` wrote).  With priors and ``opt.lambda_depth > 0`` every iteration renders with ``depth_grad=True`` and adds
+    ``opt.lambda_depth * depth_l1_loss(depth, alpha, prior)`` to its loss; otherwise the loop is unchanged."""
     if loss not in ("torch", "fused"):
         raise ValueError(f"train: loss must be 'torch' or 'fused', got {loss!r}")
+    lambda_depth = float(getattr(opt, "lambda_depth", 0.0)) if depth_priors is not None else 0.0
+    if lambda_depth > 0.0 and len(depth_priors) != len(cameras):
+        raise ValueError(f"train: {len(depth_priors)} depth priors for {len(cameras)} cameras")
     from .gaussian_renderer import render
     loss_of = fused_loss if loss == "fused" else loss_fn
     from .optim import FusedAdam
@@ -238,11 +260,16 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
         background = bg
         if opt.random_background:
             background = torch.tensor([rng.random() for _ in range(3)], dtype=torch.float32, device=bg.device)
-        pkg = render(cameras[view], gaussians, pipe, background)
+        if lambda_depth > 0.0:
+            pkg = render(cameras[view], gaussians, pipe, background, return_depth=True, depth_grad=True)
+        else:
+            pkg = render(cameras[view], gaussians, pipe, background)
         image, viewspace, visible, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
         if t:
             t.append(mark())
         loss = loss_of(image, images[view], opt.lambda_dssim)
+        if lambda_depth > 0.0:
+            loss = loss + lambda_depth * depth_l1_loss(pkg["depth"], pkg["alpha"], depth_priors[view])
         if t:
             t.append(mark())
         loss.backward()

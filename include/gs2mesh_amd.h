@@ -217,6 +217,52 @@ int gs2m_rasterize_backward(gs2m_raster* r, int P, int D, int M, int R, const fl
                             float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                             float* dL_dscale, float* dL_drot, int debug, gs2m_stream stream);
 
+/*
+ * gs2m_rasterize_backward with gradients through the maps of gs2m_rasterize_depth as well (an extension, like the maps): the
+ * argument list of gs2m_rasterize_backward with three upstream maps after dL_dpix.
+ *
+ *   dL_dpix[3,H,W]             device or NULL
+ *   dL_ddepth_expected[H,W]    device or NULL: gradient of the loss by depth_expected   (gD)
+ *   dL_ddepth_median[H,W]      device or NULL: ... by depth_median                     (gM)
+ *   dL_dalpha[H,W]             device or NULL: ... by alpha                            (gA)
+ * NULL means a map of zeros.  With the three new maps NULL (and dL_dpix given) the call IS gs2m_rasterize_backward: the same
+ * kernels, bit-identical outputs.
+ *
+ * Per pixel, with the walk of gs2m_rasterize_depth (w_j = alpha_j T_j, S = sum w_j, Z = sum w_j z_j, T_f the final
+ * transmittance, D = S > 0 ? Z / S : 0, A = 1 - T_f, med = z_m):
+ *   - depth_expected is one more "colour channel" over a zero background with the per-instance value
+ *     u_j = (gD / S)(z_j - D), 0 where S == 0: it adds T_j (u_j - rec_j) to dL/dalpha_j, rec being the reference's
+ *     behind-the-contributor recurrence (backward.cu:515);
+ *   - alpha: dA/dalpha_j = T_f / (1 - alpha_j), the shape of the background term (bg . dL_dpix becomes bg . dL_dpix - gA);
+ *   - dL/dz_j: every contributing pixel adds w_j gD / S, the pixel whose median is instance j also adds gM.  depth_median is
+ *     piecewise constant in everything but z_m: that is its stated derivative.  z_j is the view-space z of the centre, so
+ *     dL_dmean3D receives (viewmatrix[2], viewmatrix[6], viewmatrix[10]) * sum dL/dz_j.
+ * dL/dalpha_j continues into mean2D, conic and opacity exactly as for colour, under the same departures from the true
+ * derivative (straight through the 0.99 cap, NDC-scaled mean2D, 1e-7 in the conic inverse, no gradient through clamped
+ * tx / ty).  S, Z and the median are recomputed with the operations of gs2m_rasterize_depth: D has that call's bits and the
+ * median is that call's instance.
+ *
+ * Preconditions, outputs, errors, arena (dL/dz_j is the tenth float of the 48-byte instance row) and the single stream
+ * synchronisation are those of gs2m_rasterize_backward.  No float atomics: two calls give identical bits.
+ *
+ * STATED TOLERANCE: against the fp64 statement of gs2m_rasterize_backward's projection feeding the walk of
+ * gs2m_rasterize_depth, differentiated by autograd (tests/depth_grad_statement.py; loss = sum(wC image + wD depth_expected +
+ * wM depth_median + wA alpha), weights zero on pixels with a threshold decision within 1e-4, wM also where a transmittance is
+ * within 1e-4 of 0.5), every gradient tensor is within 4 x the error of the SAME statement evaluated in fp32, in
+ * max|g - g64| / max|g64| and in relative L2 (tests/test_raster_depth_backward.py), and per Gaussian on the designed edge
+ * cases of tests/test_raster_depth_backward_edges.py.  Figures: profiles/raster_depth_backward.txt.
+ */
+int gs2m_rasterize_backward_depth(gs2m_raster* r, int P, int D, int M, int R, const float* background,
+                                  int width, int height, const float* means3D, const float* shs,
+                                  const float* colors_precomp, const float* scales, float scale_modifier,
+                                  const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                  const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                                  const float* dL_dpix, const float* dL_ddepth_expected,
+                                  const float* dL_ddepth_median, const float* dL_dalpha, float* dL_dmean2D,
+                                  float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                                  float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug,
+                                  gs2m_stream stream);
+
 /* Instance rows of the last gs2m_rasterize_backward call and the bytes of the row arena (0: never allocated). */
 int gs2m_raster_backward_rows(gs2m_raster* r, int64_t* rows, int64_t* arena_bytes);
 
@@ -236,7 +282,7 @@ int gs2m_raster_backward_rows(gs2m_raster* r, int64_t* rows, int64_t* arena_byte
  * Every non-NULL output is written completely, with plain stores, each pixel once: two calls give identical bits.  A pixel
  * without a contributor holds exactly 0 in all three; listed Gaussians have z > 0.2, so 0 means "no depth" (what the TSDF
  * integrator treats as invalid).  1 - T is exact for T in [0.5, 1]: depth_median > 0 exactly where alpha >= 0.5.  The handle's
- * state is only read: a gs2m_rasterize_backward may follow.  No gradient flows through these maps.
+ * state is only read: a gs2m_rasterize_backward may follow.  Gradients through these maps: gs2m_rasterize_backward_depth.
  *
  * Errors, as gs2m_rasterize_backward: no gs2m_rasterize_forward state in the handle (e.g. after gs2m_render_views or
  * gs2m_raster_reserve), width / height different from that call, GS2M_OPT_TILE_ROWS 2, GS2M_OPT_PAIR_BATCH > 1, an overflowed

@@ -1,11 +1,18 @@
 """Cost of depth without a matcher on a C2-shaped job (300 k Gaussians, 1600 x 1200).
 
   python tools/depth_bench.py [--reps 50] [--repeats 5] [--views 16] [--out profiles/raster_depth_bench.json]
+                              [--parent-lib PATH] [--skip-pipeline]
 
   * the depth pass (gs2m_rasterize_depth: all three maps of one view), in us per view, and gs2m_rasterize_forward as a whole:
     stream events around `reps` calls after a warm-up, `repeats` times (median and range: the spread comes with the figure);
   * RenderedDepth.run(keep_on_device=True, write_files=False) + TSDF.run(fuse="batch") over `views` ring cameras, in views/s:
     a host clock around work that ends in the mesh download, after one warm-up pass of the same shapes.
+  * the backward pass, in us per view, each call with its one stream synchronisation: gs2m_rasterize_backward (colour only)
+    and gs2m_rasterize_backward_depth with all three map gradients; with --parent-lib (a libgs2mesh_amd.so built from the
+    parent commit) also the parent's gs2m_rasterize_backward on the same inputs, the three ALTERNATING inside every repeat
+    (this, parent, depth, parent, this, ...) so that drift of the shared machine hits them alike.  `backward_same_code_spread`
+    is the spread of this commit's colour backward against itself (its even repeats over its odd ones): a
+    difference to the parent inside it is code placement, not a cost.
 Prints one JSON object.  No speed gate: nothing of this had been measured before.
 """
 import argparse
@@ -68,6 +75,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--views", type=int, default=16)
     ap.add_argument("--max-blocks", type=int, default=131072, help="block pool of the fused volume (16^3 voxels, 64 KiB each)")
+    ap.add_argument("--parent-lib", default=None, help="libgs2mesh_amd.so of the parent commit: its colour backward is timed too")
+    ap.add_argument("--skip-pipeline", action="store_true", help="operator-level figures only")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -105,6 +114,29 @@ def main():
     t_fwd = [timed(fwd, a.reps) * 1e3 for _ in range(a.repeats)]
     t_depth = [timed(depth, a.reps) * 1e3 for _ in range(a.repeats)]
     t_one = [timed(lambda: r.depth_maps(W, H, want=("median",), like=xyz), a.reps) * 1e3 for _ in range(a.repeats)]
+    # ---- the backward pass: colour only (this commit, and the parent's library if given) and with the three map gradients
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    g_pix = torch.rand((3, H, W), generator=gen).to(dev) - 0.5
+    g_maps = [(torch.rand((H, W), generator=gen).to(dev) - 0.5) for _ in range(3)]
+    bw = lambda rr: rr.backward(g_pix, xyz, *common, **kw)
+    bw_depth = lambda: r.backward(g_pix, xyz, *common, grad_depth=g_maps[0], grad_median=g_maps[1], grad_alpha=g_maps[2], **kw)
+    runners = [("backward_us", lambda: bw(r)), ("backward_depth_us", bw_depth)]
+    if a.parent_lib:
+        import ctypes
+        from gs2mesh_amd import _lib
+        rp = Rasterizer(0, lib=_lib.bind(ctypes.CDLL(os.path.abspath(a.parent_lib)), require_all=False))
+        rp.forward(xyz, opac, *common, sync=True, **kw)
+        same = all(torch.equal(x, y) for x, y in zip(bw(r).values(), bw(rp).values()) if x is not None)
+        runners.insert(1, ("backward_parent_us", lambda: bw(rp)))
+        runners.append(("backward_parent_us", lambda: bw(rp)))       # this, parent, depth, parent
+    fwd()
+    for _, fn in runners:
+        fn()
+    t_bw = {name: [] for name, _ in runners}
+    for _ in range(2 * a.repeats):
+        for name, fn in runners:
+            t_bw[name].append(timed(fn, max(a.reps // 5, 5)) * 1e3)
+    rows, arena = r.backward_rows()
     # ---- pipeline level: RenderedDepth -> TSDF over the ring
     args = tsdf_args()
 
@@ -123,8 +155,18 @@ def main():
     res = dict(config=a.config, P=cfg.P, width=W, height=H, instances=instances, pixels_with_median=round(covered, 4),
                reps=a.reps, repeats=a.repeats, forward_us=spread(t_fwd, 1), depth_pass_us=spread(t_depth, 1),
                depth_pass_median_only_us=spread(t_one, 1),
-               depth_over_forward=round(statistics.median(t_depth) / statistics.median(t_fwd), 3), views=a.views)
+               depth_over_forward=round(statistics.median(t_depth) / statistics.median(t_fwd), 3), views=a.views,
+               backward_rows=rows, backward_arena_bytes=arena)
+    res.update({name: spread(v, 1) for name, v in t_bw.items()})
+    half = t_bw["backward_us"]
+    res["backward_same_code_spread"] = round(statistics.median(half[::2]) / statistics.median(half[1::2]), 4)
+    res["backward_depth_over_backward"] = round(statistics.median(t_bw["backward_depth_us"]) / statistics.median(half), 3)
+    if a.parent_lib:
+        res["backward_over_parent"] = round(statistics.median(half) / statistics.median(t_bw["backward_parent_us"]), 4)
+        res["backward_bits_equal_parent"] = bool(same)
     try:
+        if a.skip_pipeline:
+            raise RuntimeError("skipped (--skip-pipeline)")
         job()           # warm-up: every shape of the timed window
         runs = [job() for _ in range(max(a.repeats, 1))]
         res.update(render_views_per_s=spread([a.views / x[0] for x in runs], 1),

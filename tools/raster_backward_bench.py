@@ -114,7 +114,7 @@ def main():
         ks = kernel_stats(a.config, a.reps)
         res["kernels"] = ks
         # 36 of a row's 48 bytes are stored (upper bound: rows nobody contributed to are not written); all 48 are read back
-        for key, name, nbytes in (("store_GBps", "k_blend_backward<4>", 36), ("gather_GBps", "k_gaussian_backward", ROW_BYTES)):
+        for key, name, nbytes in (("store_GBps", "k_blend_backward<4", 36), ("gather_GBps", "k_gaussian_backward", ROW_BYTES)):
             hit = [k for k in ks if k.startswith(name)]
             if hit and ks[hit[0]]["avg_us"] > 0:
                 res[key] = round(rows * nbytes / (ks[hit[0]]["avg_us"] * 1e-6) / 1e9, 1)

@@ -1,7 +1,7 @@
 """Train a Gaussian splat on one GPU: point cloud + posed images -> point_cloud/iteration_N/point_cloud.ply.
 
     python tools/train_splat.py <colmap_dir> <out_dir> [--iterations N] [--resolution-scale s] [--loss {torch,fused}]
-                                [--optimizer {default,fused,sparse_adam}]
+                                [--optimizer {default,fused,sparse_adam}] [--depth-priors DIR --lambda-depth X]
     python tools/train_splat.py --synthetic <out_dir> [--iterations N] [--loss {torch,fused}] [--optimizer ...]
 
 <colmap_dir> holds a COLMAP text model (sparse/0/cameras.txt, images.txt, points3D.txt; PINHOLE or SIMPLE_PINHOLE cameras)
@@ -11,6 +11,9 @@ iteration and its split into render forward, loss, backward and optimiser + dens
 --loss fused computes L1 + D-SSIM and its gradient with the HIP kernels (training.fused_loss) instead of torch ops.
 --optimizer fused takes the Adam step and the densification statistics with the HIP kernels (optim.FusedAdam) instead of
 torch.optim.Adam and boolean-mask indexing; --optimizer sparse_adam steps only the Gaussians the view saw.
+--depth-priors DIR --lambda-depth X adds X * training.depth_l1_loss against one depth map per camera, read from
+DIR/<NNN>/out_<model>/depth.npy (NNN = the camera's position in the list, the layout `Stereo` and `RenderedDepth` write;
+--depth-model names <model>, default the only out_* folder); 0, NaN and inf in a map mean "no depth".
 """
 import argparse
 import json
@@ -59,6 +62,24 @@ def load_colmap(root, scale, device):
     return cameras, images, BasicPointCloud(xyz.astype(np.float32), rgb.astype(np.float32) / 255.0, np.zeros_like(xyz, np.float32))
 
 
+def load_depth_priors(root, cameras, model, device):
+    """one [H,W] f32 map per camera from <root>/<NNN>/out_<model>/depth.npy; non-finite -> 0 (invalid)"""
+    priors = []
+    for k, cam in enumerate(cameras):
+        view = os.path.join(root, f"{k:03d}")
+        name = model
+        if name is None:
+            outs = sorted(d for d in os.listdir(view) if d.startswith("out_"))
+            if len(outs) != 1:
+                raise SystemExit(f"{view}: {len(outs)} out_* folders, name one with --depth-model")
+            name = outs[0][4:]
+        d = np.nan_to_num(np.load(os.path.join(view, f"out_{name}", "depth.npy")).astype(np.float32), nan=0.0, posinf=0.0, neginf=0.0)
+        if d.shape != (cam.image_height, cam.image_width):
+            raise SystemExit(f"{view}: depth.npy is {d.shape}, the camera {cam.image_height} x {cam.image_width}")
+        priors.append(torch.from_numpy(np.ascontiguousarray(d)).to(device))
+    return priors
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("paths", nargs="+", help="<colmap_dir> <out_dir>, or <out_dir> with --synthetic")
@@ -71,7 +92,12 @@ def main():
     ap.add_argument("--optimizer", choices=("default", "fused", "sparse_adam"), default="default",
                     help="torch.optim.Adam (default), the fused HIP step, or the fused step on the visible rows only")
     ap.add_argument("--synthetic-size", type=int, nargs=4, default=[20000, 4000, 800, 600], metavar=("P_TRUE", "P_INIT", "W", "H"))
+    ap.add_argument("--depth-priors", metavar="DIR", help="folder of <NNN>/out_<model>/depth.npy, one per camera")
+    ap.add_argument("--depth-model", default=None, help="<model> of out_<model> under --depth-priors")
+    ap.add_argument("--lambda-depth", type=float, default=0.0, help="weight of the depth L1 term (needs --depth-priors)")
     a = ap.parse_args()
+    if (a.lambda_depth > 0) != bool(a.depth_priors):
+        ap.error("--depth-priors and a positive --lambda-depth go together")
     if not torch.cuda.is_available():
         raise SystemExit("train_splat needs a GPU")
     device = "cuda"
@@ -88,7 +114,9 @@ def main():
         out_dir = a.paths[1]
         cameras, images, pcd = load_colmap(a.paths[0], a.resolution_scale, device)
     # schedules written in iterations scale with a short run the way the reference's defaults sit in 30 000
-    opt = training.OptimizationParams(iterations=a.iterations, position_lr_max_steps=a.iterations, optimizer_type=a.optimizer)
+    opt = training.OptimizationParams(iterations=a.iterations, position_lr_max_steps=a.iterations, optimizer_type=a.optimizer,
+                                      lambda_depth=a.lambda_depth)
+    priors = load_depth_priors(a.depth_priors, cameras, a.depth_model, device) if a.depth_priors else None
     if a.iterations < 30_000:
         f = a.iterations / 30_000
         opt.densify_from_iter = max(1, int(500 * f))
@@ -106,7 +134,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     losses = training.train(g, cameras, images, opt, extent=extent, bg=bg, white_background=a.white_background, seed=a.seed,
-                            timing=timing, loss=a.loss)
+                            timing=timing, loss=a.loss, depth_priors=priors)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     ply_dir = os.path.join(out_dir, "point_cloud", f"iteration_{a.iterations}")
@@ -120,7 +148,7 @@ def main():
     split = {name: statistics.fmean(v) for name, v in timing.items()}
     print(json.dumps({
         "ply": ply, "views": len(cameras), "width": cameras[0].image_width, "height": cameras[0].image_height,
-        "iterations": a.iterations, "loss_path": a.loss, "optimizer": a.optimizer, "gaussians_start": P0, "gaussians_end": int(g.get_xyz.shape[0]),
+        "iterations": a.iterations, "loss_path": a.loss, "optimizer": a.optimizer, "lambda_depth": a.lambda_depth, "gaussians_start": P0, "gaussians_end": int(g.get_xyz.shape[0]),
         "loss_first_tenth": statistics.fmean(losses[:k]), "loss_last_tenth": statistics.fmean(losses[-k:]),
         "wall_ms_per_iteration": 1e3 * wall / max(1, a.iterations),
         "stream_ms_per_iteration": {"render_forward": split["render"], "loss": split["loss"], "backward": split["backward"],
