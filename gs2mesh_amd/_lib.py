@@ -105,6 +105,9 @@ _PROTOS = {
     "gs2m_nn_dist2": (i32, [i32, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp]),
     "gs2m_mesh_sample_count": (i32, [i64, vp, i64, vp, f64, vp, vp, vp, i64, vp, C.POINTER(i64), C.POINTER(C.c_uint32)]),
     "gs2m_mesh_sample_emit": (i32, [i64, vp, i64, vp, f64, vp, vp, i64, vp, vp]),
+    "gs2m_points_cull_views": (i32, [i32, vp, i32, vp, vp, i32, i32, f32, f32, vp, vp]),
+    "gs2m_mask_dilate_disk_scratch_bytes": (i64, [i32, i32, i32]),
+    "gs2m_mask_dilate_disk": (i32, [i32, i32, i32, C.POINTER(vp), i32, vp, vp, vp, i64, vp]),
     "gs2m_photo_loss_scratch_bytes": (i64, [i32, i32, i32]),
     "gs2m_photo_loss_forward": (i32, [i32, i32, i32, vp, vp, f32, vp, i64, vp, vp, vp, vp]),
     "gs2m_photo_loss_backward": (i32, [i32, i32, i32, vp, vp, vp, f32, vp, vp, vp]),

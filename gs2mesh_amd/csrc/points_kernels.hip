@@ -3,6 +3,7 @@
 //   knn_kernels.h          gs2m_knn_*          mean squared distance to the three nearest neighbours (simple_knn's distCUDA2)
 //   nn_kernels.h           gs2m_nn_*           nearest reference of every query (mesh evaluation); shares knn_scratch_layout
 //   mesh_sample_kernels.h  gs2m_mesh_sample_*  points on the surface of a triangle mesh (mesh evaluation)
+//   points_cull_kernels.h  gs2m_points_cull_views  keep-mask of a point set against the masks of all views (DTU's cull_scan)
 #include <math.h>
 #include <string.h>
 
@@ -11,6 +12,7 @@
 #include "knn_kernels.h"
 #include "nn_kernels.h"
 #include "mesh_sample_kernels.h"
+#include "points_cull_kernels.h"
 #include "api_check.h"
 #include "tsdf_internal.h"          // gs2m_launch_scan_u32
 
@@ -60,6 +62,33 @@ extern "C" int gs2m_nn_dist2(int Q, const float* queries, const int32_t* query_o
     }
     nn_launch((hipStream_t)stream, Q, queries, query_order, R, refs, ref_order, knn_scratch_layout(R > 0 ? scratch : nullptr, R), out_d2,
               out_idx);
+    return 0;
+}
+
+extern "C" int gs2m_points_cull_views(int V, const float* points, int n_views, const float* proj, const uint64_t* mask_bits,
+                                      int mask_width, int mask_height, float norm_w, float norm_h, uint8_t* keep,
+                                      gs2m_stream stream) {
+    if (V < 0 || n_views < 0) {
+        gs2m_set_error("gs2m_points_cull_views: V = %d, n_views = %d", V, n_views);
+        return 1;
+    }
+    if (V == 0) return 0;
+    if (!points || !keep) {
+        gs2m_set_error("gs2m_points_cull_views: NULL points or keep with V = %d", V);
+        return 1;
+    }
+    if (n_views > 0) {
+        if (!proj || !mask_bits) {
+            gs2m_set_error("gs2m_points_cull_views: NULL proj or mask_bits with n_views = %d", n_views);
+            return 1;
+        }
+        if (mask_width < 1 || mask_height < 1 || mask_width > (1 << 24) || mask_height > (1 << 24)) {
+            gs2m_set_error("gs2m_points_cull_views: masks of %d x %d (each 1 .. 2^24)", mask_width, mask_height);
+            return 1;
+        }
+    }
+    GS2M_LAUNCH(k_points_cull_views, dim3(((unsigned)V + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, V, points, n_views, proj,
+                (const unsigned long long*)mask_bits, mask_width, mask_height, (mask_width + 63) / 64, norm_w, norm_h, keep);
     return 0;
 }
 

@@ -1,6 +1,7 @@
 // stereo_kernels.hip -- the stereo stage (compiled with -ffp-contract=off) and its entry points:
 //   k_stereo_depth_occlusion (below)  gs2m_stereo_depth_occlusion  disparity -> depth + left-right consistency mask
 //   mask_kernels.h                    gs2m_mask_preprocess         the object / occlusion masks the TSDF integrates with
+//   mask_disk_kernels.h               gs2m_mask_dilate_disk        disk dilation on the same bitmaps (the DTU evaluation's cull)
 //   sgm_kernels.h                     gs2m_stereo_sgm              the built-in semi-global matcher
 //
 // Depth and occlusion are the small data-parallel step between the stereo matcher and the TSDF
@@ -24,6 +25,7 @@
 #include "../../include/gs2mesh_amd.h"
 #include "platform.h"
 #include "mask_kernels.h"
+#include "mask_disk_kernels.h"
 #include "sgm_kernels.h"
 #include "api_check.h"
 
@@ -99,6 +101,46 @@ extern "C" int gs2m_mask_preprocess(int n, int width, int height, const uint8_t*
         unsigned long long* a_bits = scratch ? (unsigned long long*)scratch + 2 * (size_t)f0 * frame_words : nullptr;
         unsigned long long* b_bits = a_bits ? a_bits + (size_t)nf * frame_words : nullptr;
         gs2m_launch_mask_preprocess((hipStream_t)stream, B, nf, width, height, invert, erode, closing_k, erosion_k, a_bits, b_bits);
+    }
+    return 0;
+}
+
+// the packed input masks of one chunk; the chunks of a call follow each other on the stream and share it
+extern "C" int64_t gs2m_mask_dilate_disk_scratch_bytes(int n, int width, int height) {
+    if (n < 0 || width <= 0 || height <= 0 || (int64_t)height * ((width + 63) / 64) > 0x7fffffffll) return -1;
+    const int nf = n < GS2M_MASK_BATCH ? n : GS2M_MASK_BATCH;
+    return (int64_t)nf * height * ((width + 63) / 64) * 8;
+}
+
+extern "C" int gs2m_mask_dilate_disk(int n, int width, int height, const uint8_t* const* masks, int radius, uint64_t* out_bits,
+                                     uint8_t* out_bytes, void* scratch, int64_t scratch_bytes, gs2m_stream stream) {
+    const int64_t need = gs2m_mask_dilate_disk_scratch_bytes(n, width, height);
+    if (need < 0) {
+        gs2m_set_error("gs2m_mask_dilate_disk: n = %d masks of %d x %d (n >= 0, width and height >= 1, at most 2^31 - 1 words a mask)",
+                       n, width, height);
+        return 1;
+    }
+    if (radius < 0 || radius > GS2M_DISK_MAX_RADIUS) {
+        gs2m_set_error("gs2m_mask_dilate_disk: radius = %d (0 .. %d)", radius, GS2M_DISK_MAX_RADIUS);
+        return 1;
+    }
+    if (n == 0) return 0;
+    if (!masks || !out_bits) {
+        gs2m_set_error("gs2m_mask_dilate_disk: NULL masks or out_bits with n = %d", n);
+        return 1;
+    }
+    for (int i = 0; i < n; ++i)
+        if (!masks[i]) {
+            gs2m_set_error("gs2m_mask_dilate_disk: mask %d is NULL", i);
+            return 1;
+        }
+    if (gs2m_scratch_refused("gs2m_mask_dilate_disk", "gs2m_mask_dilate_disk_scratch_bytes", scratch, scratch_bytes, need, 8)) return 1;
+    const size_t frame_words = (size_t)height * (size_t)((width + 63) / 64);
+    for (int f0 = 0; f0 < n; f0 += GS2M_MASK_BATCH) {
+        const int nf = n - f0 < GS2M_MASK_BATCH ? n - f0 : GS2M_MASK_BATCH;
+        gs2m_launch_mask_dilate_disk((hipStream_t)stream, masks + f0, nf, width, height, radius, (unsigned long long*)scratch,
+                                     (unsigned long long*)out_bits + (size_t)f0 * frame_words,
+                                     out_bytes ? out_bytes + (size_t)f0 * height * width : nullptr);
     }
     return 0;
 }

@@ -7,14 +7,22 @@ trees, and (DTU) a surface sampler run in a multiprocessing pool.  Here both are
 ties to the smallest index) and ``gs2m_mesh_sample_count`` / ``_emit`` (bit-identical to the reference's sampler);
 include/gs2mesh_amd.h states their arithmetic.  Everything around them is torch on the same device.
 
+Before it scores a DTU mesh the reference culls it (``cull_scan``, evaluation/DTU/eval_code/evaluate_single_scene.py:21-116):
+every view's object mask is dilated with a disk of radius 24 and a vertex survives only if every view sees it outside the
+image or on the dilated mask.  That is ``dtu_cull`` here, on two more kernels: ``gs2m_mask_dilate_disk`` (equal to scipy's /
+skimage's ``binary_dilation(mask, disk(r))`` bit for bit) and ``gs2m_points_cull_views`` (the reference's f32 projection and
+torch's nearest ``grid_sample``, stated operation by operation in the header).  ``dtu_projections`` rebuilds the reference's
+``intrinsics @ inverse(pose)`` without cv2 as ``P / ||P[2,:3]||``; equality with cv2's own decomposition was not checked.
+``visibility_cull`` is MobileBrick's ``visibility_test`` in torch ops, on the same mesh filter
+(``TriangleMesh.remove_vertices_by_mask``).
+
 Precision.  The sampler and every filter work in f64 like the reference.  The nearest-neighbour kernel works in f32, so the
 coordinates reach it as ``f32(p - origin)`` with the subtraction in f64; ``origin`` defaults to the midpoint of the ground
 truth's bounding box, ``(gt.min(0) + gt.max(0)) / 2``, which keeps the f32 coordinates of a scene of extent E below E / 2
 (spacing E * 2^-25: 2e-5 mm on a 600 mm DTU scan).  Distances are ``sqrt`` in f64 of the f32 squared distance, means are f64
 sums on the device.
 
-Outside this module, as in DESIGN.md: DTU's ``cull_scan`` (needs the dataset's per-view masks), TNT's registration and
-cropping, MobileBrick's visibility volume and ICP, Poisson-disk sampling.
+Outside this module, as in DESIGN.md: TNT's registration and cropping, MobileBrick's ICP, Poisson-disk sampling.
 """
 from __future__ import annotations
 
@@ -123,6 +131,156 @@ def sample_mesh(mesh_or_arrays, density, lib=None, device=None):
     _lib.check(lib.gs2m_mesh_sample_emit(V, _ptr(v), T, _ptr(t), float(density), _ptr(counts), _ptr(offsets), total.value,
                                          _ptr(points), stream), lib)
     return points
+
+
+# ---- DTU's cull_scan: disk dilation of the view masks and the per-view vertex cull -------------------------------------------
+
+def dilate_masks(masks, radius, want_bytes=False, lib=None, device=None):
+    """``gs2m_mask_dilate_disk``: ``scipy.ndimage.binary_dilation(mask != 0, disk(radius))`` of every mask of ``masks``
+    ([n,H,W] u8, array or tensor, or a sequence of [H,W]) -> bits [n,H,nw] int64 on the device, nw = (W + 63) // 64: bit
+    ``x & 63`` of word ``x >> 6`` is pixel x, the bits at x >= W are 0 (what ``cull_points`` reads).  ``want_bytes`` adds the
+    same as 0 / 1 bytes [n,H,W] u8: -> (bits, bytes).  0 <= radius <= 64; asynchronous on the current stream."""
+    torch = _torch()
+    lib = lib or _lib.get()
+    if not isinstance(masks, (torch.Tensor, np.ndarray)):
+        masks = torch.stack(list(masks)) if len(masks) and isinstance(masks[0], torch.Tensor) else np.asarray(masks)
+    m = _tensor(masks, torch.uint8, device)
+    if m.ndim != 3 or m.shape[1] < 1 or m.shape[2] < 1:
+        raise ValueError(f"masks must be [n,H,W] with H, W >= 1, got {tuple(m.shape)}")
+    n, H, W = (int(s) for s in m.shape)
+    nw = (W + 63) // 64
+    bits = torch.empty((n, H, nw), dtype=torch.int64, device=m.device)
+    out = torch.empty((n, H, W), dtype=torch.uint8, device=m.device) if want_bytes else None
+    need = int(lib.gs2m_mask_dilate_disk_scratch_bytes(n, W, H))
+    scratch = torch.empty((max(need, 0) // 8,), dtype=torch.int64, device=m.device)
+    ptrs = (C.c_void_p * max(n, 1))(*[m.data_ptr() + i * H * W for i in range(n)])
+    _lib.check(lib.gs2m_mask_dilate_disk(n, W, H, ptrs, int(radius), _ptr(bits), _ptr(out), _ptr(scratch), max(need, 0),
+                                         _stream_of(m, None)), lib)
+    return (bits, out) if want_bytes else bits
+
+
+def dtu_projections(cameras):
+    """The projections ``cull_scan`` builds from a DTU ``cameras.npz`` (evaluate_single_scene.py:29-38, 65-70) ->
+    (proj [n,3,4] f32, scale_mat_0 [4,4] f32).  ``cameras``: the dict, or the path of the .npz, of ``world_mat_i`` /
+    ``scale_mat_i``, i = 0 .. n - 1.
+
+    The reference takes ``P = (world_mat @ scale_mat)[:3]`` in f32, splits it with ``cv2.decomposeProjectionMatrix`` into
+    K, R and the camera centre C, and multiplies ``K / K[2,2] @ [R | -R C]`` back together.  That product is P rescaled so
+    that the left 3-vector of its third row has unit length, ``M = P / ||P[2,:3]||``, whenever ``det(P[:,:3]) > 0``; it is
+    computed here in f64 and rounded to f32 once.  ``det <= 0`` raises ValueError: which sign cv2 returns there was not
+    checked, and no DTU camera is known to be on that side.  The identity was checked against an RQ decomposition
+    (scipy); equality with cv2's own output was NOT checked -- cv2 is not a dependency of this package."""
+    if isinstance(cameras, (str, bytes)) or hasattr(cameras, "__fspath__"):
+        cameras = np.load(cameras)
+    n = 0
+    while f"world_mat_{n}" in cameras:
+        n += 1
+    proj = np.zeros((n, 3, 4), np.float32)
+    for i in range(n):
+        P = (np.asarray(cameras[f"world_mat_{i}"]).astype(np.float32) @ np.asarray(cameras[f"scale_mat_{i}"]).astype(np.float32))
+        P = P[:3, :4].astype(np.float64)
+        if not np.linalg.det(P[:, :3]) > 0:
+            raise ValueError(f"dtu_projections: camera {i} has det(P[:, :3]) = {np.linalg.det(P[:, :3])} (must be > 0)")
+        proj[i] = (P / np.sqrt((P[2, 0] * P[2, 0] + P[2, 1] * P[2, 1]) + P[2, 2] * P[2, 2])).astype(np.float32)
+    scale0 = np.asarray(cameras["scale_mat_0"]).astype(np.float32) if n else np.eye(4, dtype=np.float32)
+    return proj, scale0
+
+
+def cull_points(points, projections, mask_bits, mask_size, norm_size=(1600, 1200), lib=None):
+    """``gs2m_points_cull_views`` -> bool [V] on the device: True where point i, in every view, lands outside the image or on
+    that view's mask (include/gs2mesh_amd.h states the f32 arithmetic; it is the reference's ``cull_scan`` loop with torch's
+    nearest ``grid_sample``).  ``points`` [V,3] f32, ``projections`` [n,3,4] f32 (``dtu_projections``), ``mask_bits``
+    [n,H,nw] int64 (``dilate_masks``), ``mask_size`` = (W, H) of the masks, ``norm_size`` = the (W, H) the reference
+    normalises pixel coordinates by (it hard-codes DTU's 1600 x 1200)."""
+    torch = _torch()
+    lib = lib or _lib.get()
+    p = _points(points, torch.float32, "points")
+    dev = p.device.index if p.is_cuda else None
+    proj = _tensor(projections, torch.float32, dev).reshape(-1, 12)
+    n = int(proj.shape[0])
+    W, H = int(mask_size[0]), int(mask_size[1])
+    bits = _tensor(mask_bits, torch.int64, dev)
+    if n and tuple(bits.shape) != (n, H, (W + 63) // 64):
+        raise ValueError(f"mask_bits must be [{n},{H},{(W + 63) // 64}], got {tuple(bits.shape)}")
+    V = int(p.shape[0])
+    keep = torch.empty((V,), dtype=torch.uint8, device=p.device)
+    _lib.check(lib.gs2m_points_cull_views(V, _ptr(p), n, _ptr(proj), _ptr(bits), W, H, float(norm_size[0]), float(norm_size[1]),
+                                          _ptr(keep), _stream_of(p, None)), lib)
+    return keep.to(torch.bool)
+
+
+def _as_mesh(mesh_or_arrays):
+    from .mesh import TriangleMesh
+    if hasattr(mesh_or_arrays, "vertices"):
+        return mesh_or_arrays
+    verts, tris = mesh_or_arrays
+    t = _torch()
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, t.Tensor) else np.asarray(a)
+    return TriangleMesh(host(verts), host(tris))
+
+
+def _load_mask(m):
+    """one view's mask -> [H,W] u8.  A path is read as the reference's ``cv2.imread(p)[:, :, 0]``: the BLUE channel, here
+    PIL's ``convert("RGB")`` channel 2; an array [H,W,C] gives its channel 0 (it is taken for cv2's BGR array)."""
+    if isinstance(m, (str, bytes)) or hasattr(m, "__fspath__"):
+        from PIL import Image
+        with Image.open(m) as im:
+            return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, 2])
+    t = _torch()
+    a = m.detach().cpu().numpy() if isinstance(m, t.Tensor) else np.asarray(m)
+    if a.ndim == 3:
+        a = a[:, :, 0]
+    if a.ndim != 2:
+        raise ValueError(f"a mask must be [H,W] or [H,W,C], got {a.shape}")
+    return np.ascontiguousarray(a != 0).astype(np.uint8)
+
+
+def dtu_cull(mesh, cameras, masks, radius=24, norm_size=(1600, 1200), lib=None, device=None):
+    """The reference's ``cull_scan`` (evaluate_single_scene.py:21-116) -> a new ``TriangleMesh`` in DTU world coordinates:
+    every view's mask dilated with ``disk(radius)`` (``dilate_masks``), the vertices (as f32) kept that in every view land
+    outside the image or on the dilated mask (``cull_points``), the faces that lost a vertex dropped
+    (``remove_vertices_by_mask``), then ``v * scale_mat_0[0,0] + scale_mat_0[:3,3]`` in f64.  ``cameras``: as
+    ``dtu_projections``; ``masks``: one per camera, arrays or file paths (``_load_mask``), all of one size."""
+    import copy
+    torch = _torch()
+    mesh = _as_mesh(mesh)
+    proj, scale0 = dtu_projections(cameras)
+    ms = [_load_mask(m) for m in masks]
+    if len(ms) != proj.shape[0]:
+        raise ValueError(f"dtu_cull: {len(ms)} masks for {proj.shape[0]} cameras")
+    out = copy.deepcopy(mesh)
+    if ms:
+        if any(m.shape != ms[0].shape for m in ms):
+            raise ValueError("dtu_cull: the masks differ in size")
+        H, W = ms[0].shape
+        bits = dilate_masks(np.stack(ms), radius, lib=lib, device=device)
+        verts = torch.from_numpy(np.ascontiguousarray(mesh.vertices, np.float64)).to(torch.float32)
+        keep = cull_points(_tensor(verts, torch.float32, device), proj, bits, (W, H), norm_size, lib=lib)
+        out.remove_vertices_by_mask(~keep.cpu().numpy())
+    out.vertices = out.vertices * np.float64(scale0[0, 0]) + scale0[:3, 3].astype(np.float64)[None]
+    return out
+
+
+def visibility_cull(mesh, volume, min_pts, resolutions, voxel_size, device=None):
+    """MobileBrick's ``visibility_test`` (evaluation/MobileBrick/eval_code/evaluate.py:34-44) as the reference writes it ->
+    a new ``TriangleMesh`` without the vertices whose nearest voxel of ``volume`` [D0,D1,D2] is not > 0 (or lies outside
+    it), vertex normals recomputed: voxels = (v - min_pts) / voxel_size in f64, scaled to [-1, 1] by ``resolutions - 1``,
+    reversed to (z, y, x), cast to f32 and looked up with ``F.grid_sample(mode='nearest', padding_mode='zeros',
+    align_corners=True)``.  Torch ops only."""
+    import copy
+    import torch.nn.functional as F
+    torch = _torch()
+    mesh = _as_mesh(mesh)
+    dev = _lib.MEMORY.buffer_device(_device(device))
+    vol = torch.from_numpy(np.ascontiguousarray(volume)).float().to(dev)
+    g = (np.asarray(mesh.vertices, np.float64) - np.asarray(min_pts, np.float64)) / voxel_size        # in voxels, f64
+    g = g / (np.asarray(resolutions, np.float64) - 1) * 2 - 1                                          # [-1, 1] over the volume
+    grid = torch.from_numpy(np.ascontiguousarray(g[:, ::-1])).float().to(dev)                           # (z, y, x): x indexes the last axis
+    seen = F.grid_sample(vol[None, None], grid[None, None, None], mode="nearest", padding_mode="zeros", align_corners=True)
+    seen = seen[0, 0, 0, 0].cpu().numpy() > 0
+    out = copy.deepcopy(mesh)
+    out.remove_vertices_by_mask(~seen)
+    return out.compute_vertex_normals()
 
 
 # ---- torch around them -------------------------------------------------------------------------------------------------
@@ -253,13 +411,20 @@ def fscore_metrics(pred_points, gt_points, thresholds, origin=None, sort=True, l
 
 
 def evaluate_mesh(mesh, gt_points, density=0.2, max_dist=20, thresholds=(), obs_mask=None, bb=None, res=None, plane=None,
-                  patch=60, origin=None, sort=True, lib=None, device=None):
+                  patch=60, origin=None, sort=True, lib=None, device=None, cull=None):
     """The DTU evaluation of a mesh (eval.py:43-134), from arrays instead of the dataset's directory: sample at ``density``,
     thin to one point per cell of edge ``density`` (``thin_points``), then -- when ``obs_mask`` / ``bb`` / ``res`` are given --
     keep the inbound and observed points, and -- when ``plane`` is given -- the ground truth above it; ``dtu_metrics`` of what
     is left.  With ``thresholds`` the MobileBrick figures of the same two sets (``fscore_metrics``) come under "fscore".
-    -> {mean_d2s, mean_s2d, overall, n_sampled, n_thinned, n_observed, n_gt[, fscore]}."""
+    With ``cull`` = dict(cameras=..., masks=...[, radius, norm_size]) the mesh first goes through ``dtu_cull``, as the
+    reference's run_and_evaluate_dtu.py has it, and "n_vertices_culled" is added.
+    -> {mean_d2s, mean_s2d, overall, n_sampled, n_thinned, n_observed, n_gt[, fscore][, n_vertices_culled]}."""
     torch = _torch()
+    n_culled = None
+    if cull is not None:
+        before = _as_mesh(mesh)
+        mesh = dtu_cull(before, lib=lib, device=device, **cull)
+        n_culled = int(before.vertices.shape[0]) - int(mesh.vertices.shape[0])
     pts = sample_mesh(mesh, density, lib=lib, device=device)
     dev = pts.device.index if pts.is_cuda else None
     gt = _points(gt_points, torch.float64, "gt_points", dev)
@@ -274,4 +439,6 @@ def evaluate_mesh(mesh, gt_points, density=0.2, max_dist=20, thresholds=(), obs_
     out.update(n_sampled=int(pts.shape[0]), n_thinned=int(down.shape[0]), n_observed=int(data_obs.shape[0]), n_gt=int(gt_q.shape[0]))
     if len(thresholds):
         out["fscore"] = fscore_metrics(data_obs, gt_q, thresholds, origin=o.cpu().numpy(), sort=sort, lib=lib)
+    if n_culled is not None:
+        out["n_vertices_culled"] = n_culled
     return out

@@ -156,6 +156,28 @@ class TriangleMesh:
             self.triangle_normals = self.triangle_normals[keep]
         return self
 
+    def remove_vertices_by_mask(self, mask):
+        """Open3D's ``remove_vertices_by_mask`` (trimesh: ``update_vertices(~mask)`` + ``update_faces``): drop the vertices
+        where ``mask`` is True.  The others keep their order -- also those that no triangle uses any more --, a triangle stays
+        iff all three of its vertices stay, renumbered, and colours and normals follow the vertices."""
+        remove = np.asarray(mask, bool).reshape(-1)
+        if remove.shape[0] != self.vertices.shape[0]:
+            raise ValueError(f"remove_vertices_by_mask: mask of {remove.shape[0]} for {self.vertices.shape[0]} vertices")
+        keep = ~remove
+        remap = np.cumsum(keep) - 1
+        tri_keep = keep[self.triangles].all(axis=1) if self.triangles.shape[0] else np.zeros(0, bool)
+        if self.triangle_normals.shape[0] == tri_keep.shape[0]:
+            self.triangle_normals = self.triangle_normals[tri_keep]
+        self.triangles = remap[self.triangles[tri_keep]].astype(np.int32).reshape(-1, 3)
+        if self.vertex_colors.shape[0] == keep.shape[0]:
+            self.vertex_colors = self.vertex_colors[keep]
+        if self.vertex_normals.shape[0] == keep.shape[0]:
+            self.vertex_normals = self.vertex_normals[keep]
+        if self.edge_index.shape[0] == keep.shape[0]:
+            self.edge_index = self.edge_index[keep]
+        self.vertices = self.vertices[keep]
+        return self
+
     def remove_unreferenced_vertices(self):
         used = np.zeros(self.vertices.shape[0], bool)
         used[self.triangles.reshape(-1)] = True

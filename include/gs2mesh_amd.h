@@ -665,6 +665,28 @@ int gs2m_mask_preprocess(int n, int width, int height, const uint8_t* const* obj
                          gs2m_stream stream);
 
 /*
+ * Binary dilation of n masks with a disk: the `binary_dilation(mask, disk(24))` with which the DTU evaluation's cull_scan
+ * widens every view's object mask (evaluation/DTU/eval_code/evaluate_single_scene.py:80), i.e. scipy.ndimage.binary_dilation
+ * with skimage's disk(r) footprint.  Defined bit for bit, per mask:
+ *   in(y, x)  = mask[y][x] != 0 inside the image, 0 outside it;
+ *   out(y, x) = OR over all integer (dy, dx) with dy * dy + dx * dx <= radius * radius of in(y + dy, x + dx).
+ * radius = 0 is the identity (out = mask != 0).
+ *   n, width, height        any n >= 0 (worked off in chunks of 32 masks), width and height >= 1
+ *   masks                   host array [n] of [height][width] u8 DEVICE pointers (non-zero = set), none of them NULL
+ *   radius                  0 .. 64
+ *   out_bits                [n][height][nw] u64 device, nw = (width + 63) / 64: bit x & 63 of word x >> 6 is pixel x, the bits
+ *                           at x >= width are 0.  This is the `mask_bits` of gs2m_points_cull_views.
+ *   out_bytes               NULL, or [n][height][width] u8 device: the same as 0 / 1 bytes
+ *   scratch, scratch_bytes  device, 8-byte aligned, at least gs2m_mask_dilate_disk_scratch_bytes(n, width, height) (-1 for
+ *                           sizes it refuses); nothing in it outlives the call
+ * n = 0 does nothing and returns 0.  Stateless, asynchronous on `stream`, no allocation, no atomics, the same bits on every
+ * run; bad arguments return 1 with gs2m_last_error().
+ */
+int64_t gs2m_mask_dilate_disk_scratch_bytes(int n, int width, int height);
+int gs2m_mask_dilate_disk(int n, int width, int height, const uint8_t* const* masks, int radius, uint64_t* out_bits,
+                          uint8_t* out_bytes, void* scratch, int64_t scratch_bytes, gs2m_stream stream);
+
+/*
  * The built-in stereo matcher of gs2mesh_amd.stereo_utils.Stereo (stereo_model "SGM"): semi-global matching over four paths
  * on a 9 x 7 census transform.  It stands where the reference runs its stereo network (stereo_utils.py:105-124) and makes no
  * claim to that network's quality; it needs no weights.  Integer arithmetic up to the last step, so the output is defined
@@ -791,6 +813,37 @@ int gs2m_mesh_sample_count(int64_t n_vertices, const double* vertices, int64_t n
 int gs2m_mesh_sample_emit(int64_t n_vertices, const double* vertices, int64_t n_triangles, const int32_t* triangles,
                           double density, const uint32_t* counts, const uint32_t* offsets, int64_t total, double* points,
                           gs2m_stream stream);
+
+/*
+ * The per-view vertex cull of the DTU evaluation (evaluation/DTU/eval_code/evaluate_single_scene.py:63-99): keep[i] = 1 iff
+ * point i, in every view, lands outside the image or on that view's mask.  In f32, every operation rounded on its own (no
+ * FMA, IEEE division), parentheses = order; (x, y, z) the point, m the view's row-major 3 x 4 projection:
+ *   c_k = ((m[k][0] * x + m[k][1] * y) + m[k][2] * z) + m[k][3],  k = 0, 1, 2
+ *   u = c_0 / (c_2 + 1e-6f),  v = c_1 / (c_2 + 1e-6f)
+ *   gx = (u / (norm_w - 1) - 0.5f) * 2,  gy = (v / (norm_h - 1) - 0.5f) * 2
+ *   valid = gx > -1 && gx < 1 && gy > -1 && gy < 1                      (false when anything is NaN)
+ *   ix = nearbyint(((gx + 1) / 2) * (mask_width - 1)),  iy = nearbyint(((gy + 1) / 2) * (mask_height - 1))     (ties to even)
+ *   s = bit (iy, ix) of the view's bitmap if 0 <= ix < mask_width and 0 <= iy < mask_height (so both finite), else 0
+ *   the view passes  <=>  s != 0 || !valid;   keep = every view passes  (n_views = 0 keeps every point)
+ * (ix, iy, s) is torch's grid_sampler with mode='nearest', padding_mode='zeros', align_corners=True, which scales by the
+ * mask's own size, while the reference normalises by its hard-coded image size: norm_w = 1600, norm_h = 1200 there.  The
+ * reference's quirks are part of the statement: a point behind a camera goes through the same formula, and a point outside the
+ * open interval passes that view.
+ *   points                  [V][3] f32 device
+ *   proj                    [n_views][12] f32 device: row-major 3 x 4 (intrinsics @ world-to-camera)
+ *   mask_bits               [n_views][mask_height][nw] u64 device, nw = (mask_width + 63) / 64, as gs2m_mask_dilate_disk writes
+ *                           them; mask_width, mask_height in 1 .. 2^24
+ *   keep                    [V] u8 device: 0 / 1
+ * Tolerance against the reference's own lines (`intrinsic @ w2c @ vertices` by torch's matmul, whose summation order is the
+ * BLAS's): a keep-bit can differ only where, in some view, the exact (f64) coordinate on the mask's pixel grid lies within
+ * tau = 7.6e-5 of a half-integer or of an image bound.  Measured: the f32 sequence above is at most 1.86e-5 of a mask pixel
+ * from the f64 value over 1000 points x 3 views of a 130 x 70 mask (tests/test_points_cull.py); tau is 4 x that, the factor
+ * for the summation order of the reference's matmul.
+ * V = 0 does nothing and returns 0.  Stateless, asynchronous on `stream`, no allocation, no atomics, the result a function of
+ * the inputs alone; bad arguments return 1 with gs2m_last_error().
+ */
+int gs2m_points_cull_views(int V, const float* points, int n_views, const float* proj, const uint64_t* mask_bits, int mask_width,
+                           int mask_height, float norm_w, float norm_h, uint8_t* keep, gs2m_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* photometric loss of 3DGS training (L1 + D-SSIM, GS/utils/loss_utils.py, train.py:89-90) */

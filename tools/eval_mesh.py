@@ -2,11 +2,13 @@
 """Geometric evaluation of a mesh against a ground-truth point set on the GPU (gs2mesh_amd.evaluation):
 
     python tools/eval_mesh.py mesh.ply gt_points.ply [--dtu-dir D --scan N] [--density 0.2] [--max-dist 20]
-                              [--thresholds 0.0025,0.005]
+                              [--thresholds 0.0025,0.005] [--cull-dir scanN [--cull-radius 24] [--save-culled culled.ply]]
 
 prints one JSON object: the DTU evaluation's keys (mean_d2s, mean_s2d, overall; evaluation/DTU/eval_code/eval.py) and,
 with --thresholds, MobileBrick's (pred_gt, gt_pred, chamfer and per threshold accuracy, recall, F1) under "fscore".
 --dtu-dir / --scan read D/ObsMask/ObsMask<N>_10.mat and D/ObsMask/Plane<N>.mat as the reference does (scipy.io.loadmat).
+--cull-dir first culls the mesh as the reference's cull_scan does (evaluation.dtu_cull): it reads scanN/cameras.npz and the
+sorted scanN/mask/*.png, and the result gains "n_vertices_culled"; --save-culled writes the culled mesh (DTU world frame).
 The mesh is this package's own PLY; the ground truth is any vertex PLY (binary little-endian or ASCII)."""
 import argparse
 import json
@@ -26,10 +28,13 @@ def main(argv=None):
     ap.add_argument("--max-dist", type=float, default=20.0)
     ap.add_argument("--patch", type=float, default=60.0)
     ap.add_argument("--thresholds", default="", help="comma-separated distances for accuracy / recall / F1")
+    ap.add_argument("--cull-dir", default=None, help="DTU scan directory with cameras.npz and mask/*.png")
+    ap.add_argument("--cull-radius", type=int, default=24, help="radius of the disk the masks are dilated with (the reference: 24)")
+    ap.add_argument("--save-culled", default=None, help="write the culled mesh to this PLY (needs --cull-dir)")
     args = ap.parse_args(argv)
 
     from gs2mesh_amd import evaluation
-    from gs2mesh_amd.mesh import read_point_cloud, read_triangle_mesh
+    from gs2mesh_amd.mesh import read_point_cloud, read_triangle_mesh, write_triangle_mesh
 
     kw = {}
     if args.dtu_dir is not None:
@@ -40,7 +45,16 @@ def main(argv=None):
         kw.update(obs_mask=obs["ObsMask"], bb=obs["BB"], res=obs["Res"],
                   plane=loadmat(os.path.join(args.dtu_dir, "ObsMask", f"Plane{args.scan}.mat"))["P"])
     thresholds = [float(t) for t in args.thresholds.split(",") if t.strip()]
-    out = evaluation.evaluate_mesh(read_triangle_mesh(args.mesh), read_point_cloud(args.gt_points), density=args.density,
+    mesh = read_triangle_mesh(args.mesh)
+    if args.save_culled is not None and args.cull_dir is None:
+        ap.error("--save-culled needs --cull-dir")
+    if args.cull_dir is not None:
+        import glob
+        kw.update(cull=dict(cameras=os.path.join(args.cull_dir, "cameras.npz"),
+                            masks=sorted(glob.glob(os.path.join(args.cull_dir, "mask", "*.png"))), radius=args.cull_radius))
+        if args.save_culled is not None:
+            write_triangle_mesh(args.save_culled, evaluation.dtu_cull(mesh, **kw["cull"]))
+    out = evaluation.evaluate_mesh(mesh, read_point_cloud(args.gt_points), density=args.density,
                                    max_dist=args.max_dist, thresholds=thresholds, patch=args.patch, **kw)
     print(json.dumps(out))
     return out
