@@ -184,9 +184,16 @@ extern "C" int gs2m_raster_set_option(gs2m_raster* r, int option, int value) {
     }
 }
 
+// the 16 x 16 reference grid of a W x H image
+static void tile_grid(int W, int H, int* gx, int* gy) {
+    *gx = (W + GS2M_TILE - 1) / GS2M_TILE;
+    *gy = (H + GS2M_TILE - 1) / GS2M_TILE;
+}
+
 // tiles of the binning grid: 16 x (16 * rows) pixels
 static int binning_tiles(const gs2m_raster* r, int W, int H) {
-    const int gx = (W + GS2M_TILE - 1) / GS2M_TILE, gy = (H + GS2M_TILE - 1) / GS2M_TILE;
+    int gx, gy;
+    tile_grid(W, H, &gx, &gy);
     return gx * ((gy + r->opt_tile_rows - 1) / r->opt_tile_rows);
 }
 
@@ -216,8 +223,9 @@ extern "C" int gs2m_raster_reserve(gs2m_raster* r, int P, int n_views, int W, in
     // this ends the forward state (gs2m_rasterize_forward sets it again once its own pass, reserve included, has been launched)
     r->fw_valid = false;
     const int nv = n_views < GS2M_MAX_PASS_VIEWS ? (n_views < 1 ? 1 : n_views) : GS2M_MAX_PASS_VIEWS;
-    const int tiles = ((W + GS2M_TILE - 1) / GS2M_TILE) * ((H + GS2M_TILE - 1) / GS2M_TILE);
-    int chunk, n_wg;
+    int gx, gy, chunk, n_wg;
+    tile_grid(W, H, &gx, &gy);
+    const int tiles = gx * gy;
     geometry(r, P, &chunk, &n_wg);
     if (r->d_recs.reserve(3 * (size_t)nv * (size_t)(P > 0 ? P : 1))) return 1;
     if (r->d_tilemask.reserve((size_t)nv * (size_t)(P > 0 ? P : 1))) return 1;
@@ -261,7 +269,8 @@ static StageTimer stage_timer(gs2m_raster* r, hipStream_t st, int stage) {
 static int run_views(gs2m_raster* r, const GaussIn& g, int nv, int pairs, int W, int H, float* out_color,
                      unsigned char* out_rgb8, int* out_radii, int status_slot, hipStream_t st, const CamUniform* host_cams) {
     const int nvt = nv * pairs;   // views of the pass: the scans, the per-tile sort and the compositing take them all (grid.y)
-    const int gx = (W + GS2M_TILE - 1) / GS2M_TILE, gy = (H + GS2M_TILE - 1) / GS2M_TILE;
+    int gx, gy;
+    tile_grid(W, H, &gx, &gy);
     const int gys = (gy + r->opt_tile_rows - 1) / r->opt_tile_rows;  // binning rows (tiles of 16 x 16*rows pixels)
     const int tiles = gx * gys;
     // Advisory hints from the PREVIOUS pass of the same geometry, snapshotted before this pass launches anything: k_tile_scan
@@ -372,6 +381,43 @@ static int run_views(gs2m_raster* r, const GaussIn& g, int nv, int pairs, int W,
     return 0;
 }
 
+// GaussIn of the operator-level arguments: activated values, one SH block or precomputed colours; no rest block, no packed
+// copy, no id map (the pipeline-level caller adds those)
+static GaussIn gauss_in(int P, int D, int M, const float* means3D, const float* scales, float scale_modifier,
+                        const float* rotations, const float* opacities, const float* shs, const float* cov3D_precomp,
+                        const float* colors_precomp) {
+    // in GaussIn's order: xyz scales rots opac shs shs_rest shs_packed cov3D_precomp colors_precomp ids | P D M raw | scale_modifier
+    return GaussIn{means3D, scales, rotations, opacities, shs, nullptr, nullptr, cov3D_precomp, colors_precomp, nullptr,
+                   P, D, M, 0, scale_modifier};
+}
+
+// What gs2m_rasterize_depth and the backward need of the handle: the state of ONE gs2m_rasterize_forward call of this size, with
+// the 16 x 16 lists.  P: the backward's Gaussian count, compared as well and named in its message; NULL for the depth pass.
+static int check_forward_state(const gs2m_raster* r, const char* who, int width, int height, const int* P) {
+    if (!r->fw_valid) {
+        gs2m_set_error("%s: the handle holds no state of a gs2m_rasterize_forward call (the last call was "
+                       "gs2m_render_views or gs2m_raster_reserve, or none)", who);
+        return 1;
+    }
+    if ((P && *P != r->fw_P) || width != r->fw_W || height != r->fw_H) {
+        if (P)
+            gs2m_set_error("%s: P %d / %dx%d do not match the last forward (P %d / %dx%d)", who, *P, width, height,
+                           r->fw_P, r->fw_W, r->fw_H);
+        else
+            gs2m_set_error("%s: %dx%d do not match the last forward (%dx%d)", who, width, height, r->fw_W, r->fw_H);
+        return 1;
+    }
+    if (r->fw_tile_rows != 1 || r->opt_tile_rows != 1) {
+        gs2m_set_error("%s needs the 16 x 16 instance lists: GS2M_OPT_TILE_ROWS 2 is not supported", who);
+        return 1;
+    }
+    if (r->opt_pair_batch > 1) {
+        gs2m_set_error("%s is not available with GS2M_OPT_PAIR_BATCH (a gs2m_render_views option)", who);
+        return 1;
+    }
+    return 0;
+}
+
 extern "C" int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const float* background, int width,
                                       int height, const float* means3D, const float* shs,
                                       const float* colors_precomp, const float* opacities, const float* scales,
@@ -426,22 +472,7 @@ extern "C" int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const
         gs2m_set_error("M = %d SH coefficients < (D+1)^2 = %d", M, (D + 1) * (D + 1));
         return 1;
     }
-    GaussIn g;
-    g.xyz = means3D;
-    g.scales = scales;
-    g.rots = rotations;
-    g.opac = opacities;
-    g.shs = shs;
-    g.shs_rest = nullptr;
-    g.shs_packed = nullptr;
-    g.cov3D_precomp = cov3D_precomp;
-    g.colors_precomp = colors_precomp;
-    g.ids = nullptr;
-    g.P = P;
-    g.D = D;
-    g.M = M;
-    g.raw = 0;
-    g.scale_modifier = scale_modifier;
+    const GaussIn g = gauss_in(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, cov3D_precomp, colors_precomp);
     const int saved_debug = r->opt_debug;
     if (debug) r->opt_debug = 1;
     gs2m_launch_pack_camera(st, r->d_cams.get(), 0, viewmatrix, projmatrix, cam_pos, background, tan_fovx, tan_fovy,
@@ -477,24 +508,7 @@ static int rasterize_backward(gs2m_raster* r, const char* who, int depth, int P,
     }
     hipStream_t st = (hipStream_t)stream;
     GS2M_HIPCHK(hipSetDevice(r->device));
-    if (!r->fw_valid) {
-        gs2m_set_error("%s: the handle holds no state of a gs2m_rasterize_forward call (the last call was "
-                       "gs2m_render_views or gs2m_raster_reserve, or none)", who);
-        return 1;
-    }
-    if (P != r->fw_P || width != r->fw_W || height != r->fw_H) {
-        gs2m_set_error("%s: P %d / %dx%d do not match the last forward (P %d / %dx%d)", who, P, width, height,
-                       r->fw_P, r->fw_W, r->fw_H);
-        return 1;
-    }
-    if (r->fw_tile_rows != 1 || r->opt_tile_rows != 1) {
-        gs2m_set_error("%s needs the 16 x 16 instance lists: GS2M_OPT_TILE_ROWS 2 is not supported", who);
-        return 1;
-    }
-    if (r->opt_pair_batch > 1) {
-        gs2m_set_error("%s is not available with GS2M_OPT_PAIR_BATCH (a gs2m_render_views option)", who);
-        return 1;
-    }
+    if (check_forward_state(r, who, width, height, &P)) return 1;
     if (D < 0 || D > 3) {
         gs2m_set_error("SH degree %d not in 0..3", D);
         return 1;
@@ -525,7 +539,8 @@ static int rasterize_backward(gs2m_raster* r, const char* who, int depth, int P,
         int v;
         ~Restore() { r->opt_debug = v; }
     } restore{r, saved_debug};
-    const int gx = (width + GS2M_TILE - 1) / GS2M_TILE, gy = (height + GS2M_TILE - 1) / GS2M_TILE;
+    int gx, gy;
+    tile_grid(width, height, &gx, &gy);
     const GeomRecs recs{r->d_recs.get(), r->d_recs.get() + 2 * (size_t)P};
     if (r->d_bw_offset.reserve((size_t)P)) return 1;
     if (r->d_bw_blocks.reserve((size_t)(P + 255) / 256)) return 1;
@@ -554,22 +569,8 @@ static int rasterize_backward(gs2m_raster* r, const char* who, int depth, int P,
                                    r->d_bw_rows.get(), n_rows, depth, dL_ddepth_expected, dL_ddepth_median, dL_dalpha);
         if (dbg_check(r, st, "blend backward")) return 1;
     }
-    GaussIn g;
-    g.xyz = means3D;
-    g.scales = scales;
-    g.rots = rotations;
-    g.opac = nullptr;
-    g.shs = shs;
-    g.shs_rest = nullptr;
-    g.shs_packed = nullptr;
-    g.cov3D_precomp = cov3D_precomp;
-    g.colors_precomp = colors_precomp;
-    g.ids = nullptr;
-    g.P = P;
-    g.D = D;
-    g.M = M;
-    g.raw = 0;
-    g.scale_modifier = scale_modifier;
+    // the opacities are not an input of the backward: their gradient comes out of the instance rows
+    const GaussIn g = gauss_in(P, D, M, means3D, scales, scale_modifier, rotations, nullptr, shs, cov3D_precomp, colors_precomp);
     BwOut o;
     o.dL_dmean2D = dL_dmean2D;
     o.dL_dconic = dL_dconic;
@@ -631,23 +632,7 @@ extern "C" int gs2m_rasterize_depth(gs2m_raster* r, int width, int height, float
     }
     hipStream_t st = (hipStream_t)stream;
     GS2M_HIPCHK(hipSetDevice(r->device));
-    if (!r->fw_valid) {
-        gs2m_set_error("gs2m_rasterize_depth: the handle holds no state of a gs2m_rasterize_forward call (the last call was "
-                       "gs2m_render_views or gs2m_raster_reserve, or none)");
-        return 1;
-    }
-    if (width != r->fw_W || height != r->fw_H) {
-        gs2m_set_error("gs2m_rasterize_depth: %dx%d do not match the last forward (%dx%d)", width, height, r->fw_W, r->fw_H);
-        return 1;
-    }
-    if (r->fw_tile_rows != 1 || r->opt_tile_rows != 1) {
-        gs2m_set_error("gs2m_rasterize_depth needs the 16 x 16 instance lists: GS2M_OPT_TILE_ROWS 2 is not supported");
-        return 1;
-    }
-    if (r->opt_pair_batch > 1) {
-        gs2m_set_error("gs2m_rasterize_depth is not available with GS2M_OPT_PAIR_BATCH (a gs2m_render_views option)");
-        return 1;
-    }
+    if (check_forward_state(r, "gs2m_rasterize_depth", width, height, nullptr)) return 1;
     const size_t bytes = sizeof(float) * (size_t)width * height;
     if (r->fw_P == 0) {   // the forward rendered nothing: no pixel has a contributor
         if (depth_expected) GS2M_HIPCHK(hipMemsetAsync(depth_expected, 0, bytes, st));
@@ -661,7 +646,8 @@ extern "C" int gs2m_rasterize_depth(gs2m_raster* r, int width, int height, float
     }
     if (!depth_expected && !depth_median && !alpha) return 0;
     const int P = r->fw_P;
-    const int gx = (width + GS2M_TILE - 1) / GS2M_TILE, gy = (height + GS2M_TILE - 1) / GS2M_TILE;
+    int gx, gy;
+    tile_grid(width, height, &gx, &gy);
     const GeomRecs recs{r->d_recs.get(), r->d_recs.get() + 2 * (size_t)P};
     gs2m_launch_blend_depth(st, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, P, r->last_cap, width, height, depth_expected,
                             depth_median, alpha);
@@ -727,18 +713,12 @@ extern "C" int gs2m_render_views(gs2m_raster* r, const gs2m_gaussians* gs, const
         gs2m_set_error("gs2m_render_views: NULL Gaussian array");
         return 1;
     }
-    GaussIn g;
-    g.xyz = gs->xyz;
-    g.scales = gs->scales;
-    g.rots = gs->rotations;
-    g.opac = gs->opacities;
-    g.shs = gs->shs;
+    GaussIn g = gauss_in(gs->P, gs->sh_degree, gs->M, gs->xyz, gs->scales, scale_modifier, gs->rotations, gs->opacities, gs->shs,
+                         nullptr, nullptr);
+    g.raw = gs->raw;
     g.shs_rest = gs->shs_rest;
     g.shs_packed = (r->pack_src == gs->shs && r->pack_src_rest == gs->shs_rest && r->pack_P == gs->P && gs->M == 16)
                        ? r->d_shpack.get() : nullptr;
-    g.cov3D_precomp = nullptr;
-    g.colors_precomp = nullptr;
-    g.ids = nullptr;
     r->run_rank = nullptr;
     if (r->model_packed && g.shs_packed && r->model_src[0] == gs->xyz && r->model_src[1] == gs->scales &&
         r->model_src[2] == gs->rotations && r->model_src[3] == gs->opacities) {
@@ -751,11 +731,6 @@ extern "C" int gs2m_render_views(gs2m_raster* r, const gs2m_gaussians* gs, const
         g.ids = r->d_order.get();
         r->run_rank = r->d_rank.get();
     }
-    g.P = gs->P;
-    g.D = gs->sh_degree;
-    g.M = gs->M;
-    g.raw = gs->raw;
-    g.scale_modifier = scale_modifier;
     const int tiles = binning_tiles(r, W, H);
     // views fused per pass: as many (<= GS2M_MAX_VIEWS) as the LDS tile cursors of the scatter allow
     int per = GS2M_MAX_VIEWS;
@@ -783,8 +758,7 @@ extern "C" int gs2m_render_views(gs2m_raster* r, const gs2m_gaussians* gs, const
             u.focal_x = W / (2.0f * c.tanfovx);
             u.W = W;
             u.H = H;
-            u.gx = (W + GS2M_TILE - 1) / GS2M_TILE;
-            u.gy = (H + GS2M_TILE - 1) / GS2M_TILE;
+            tile_grid(W, H, &u.gx, &u.gy);
             u.bg[0] = bg[0];
             u.bg[1] = bg[1];
             u.bg[2] = bg[2];

@@ -4,7 +4,8 @@
 // variant 4, raster_blend.h).  The forward does not write final_T / n_contrib (raster_blend.h:8), so the wave walks the tile's
 // sorted list TWICE with one alpha function (bw_alpha):
 //   1. front to back: per pixel the transmittance after its last contributor (T_final) and the list position after that
-//      contributor (n_contrib) -- the three decisions of renderCUDA, including stop-before-accumulate;
+//      contributor (n_contrib) -- the three decisions of renderCUDA, including stop-before-accumulate.  This is the shared
+//      tile walk (raster_tile_walk.h: walk_tile, walk_gather, walk_step), the one k_blend_depth runs;
 //   2. back to front from the wave's largest n_contrib: T is rebuilt by division (T / (1 - alpha), backward.cu:503), the colour
 //      behind a contributor is carried as the reference's accum_rec recurrence (:515), and every contributing pixel adds to the
 //      nine per-instance values  dL/dmean2D (2)  dL/dconic (3)  dL/dopacity (1)  dL/dcolour (3).
@@ -37,24 +38,13 @@
 //   * dL/dz_j, the tenth value of the instance row (row[9]): every contributing pixel adds w_j gD / S, the pixel whose median
 //     is this instance also adds gM.  med is piecewise constant in everything but z_m; that is the stated derivative.  The
 //     per-Gaussian pass adds (vm[2], vm[6], vm[10]) sum(row[9]) to dL/dmean3D: z_j is the view-space z of the centre.
-// dL/dalpha continues into mean2D, conic and opacity exactly as for colour, under the same departures.  Walk 1 accumulates S
-// and Z with k_blend_depth's operations (S += w; Z = fmaf(w, z, Z)) and records the median's list position next to n_contrib,
-// so D has the forward's bits and the median is the forward's instance.  Values nine and ten share one 2-value butterfly
-// (bw_reduce2).  The DEPTH = false instantiation is the colour backward unchanged: it neither reads nor writes row[9].
+// dL/dalpha continues into mean2D, conic and opacity exactly as for colour, under the same departures.  Walk 1 is k_blend_depth's
+// own walk_step with S and Z carried (S = fma(T, alpha, S); w = alpha T rounded; Z = fma(w, z, Z)) and the median's list position
+// recorded where the depth pass records its z, so D has the forward's bits and the median is the forward's instance.  Values
+// nine and ten share one 2-value butterfly (bw_reduce2).  The DEPTH = false instantiation is the colour backward unchanged: its
+// walk_step carries no S, Z or median, and it neither reads nor writes row[9].
 #pragma once
-#include "raster_common.h"
-
-// alpha of one staged instance at one pixel: renderCUDA's `power`, G = exp(power), alpha = min(0.99, o G) and the two skip
-// decisions (forward.cu:331-343 = backward.cu:491-501).  Explicit FMAs: both walks of the kernel round alike.
-GS2M_DEVICE bool bw_alpha(const float4 A, const float4 B, const float pxf, const float pyf, float& dx, float& dy, float& G,
-                          float& alpha) {
-    dx = A.x - pxf;
-    dy = A.y - pyf;
-    const float power = fmaf(-0.5f * A.z * dx, dx, fmaf(-0.5f * B.x * dy, dy, -(A.w * dx) * dy));
-    G = gs2m_fast_exp(power);
-    alpha = fminf(0.99f, B.y * G);
-    return !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
-}
+#include "raster_tile_walk.h"
 
 // sum over the 64 lanes of eight per-lane values: afterwards lane l holds the complete sum of value 4 (l & 1) + 2 ((l >> 1) & 1) +
 // ((l >> 2) & 1).  Each step halves the values a lane carries (it keeps one half, sends the other to its partner): 4 + 2 + 1
@@ -113,26 +103,20 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
     __shared__ float4 s_a[WPB][64], s_b[WPB][64];
     __shared__ float2 s_c[WPB][64];
     __shared__ float s_z[DEPTH ? WPB : 1][64];
-    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
     const CamUniform& cam = cams[0];
-    const int W = cam.W, H = cam.H, gx = cam.gx;
-    const int tiles = gx * cam.gy;
-    const int tile = gs2m_uniform((int)blockIdx.x * WPB + wave);
-    if (tile >= tiles) return;
-    const int ty = tile / gx, tx = tile - ty * gx;
-    float4* sa = &s_a[wave][0];
-    float4* sb = &s_b[wave][0];
-    float2* sc = &s_c[wave][0];
-    float* sz = &s_z[DEPTH ? wave : 0][0];
-    unsigned r0 = tile_start[tile], r1 = tile_start[tile + 1];
-    if (r0 > cap) r0 = cap;
-    if (r1 > cap) r1 = cap;
-    r0 = (unsigned)gs2m_uniform((int)r0);
-    r1 = (unsigned)gs2m_uniform((int)r1);
+    const int W = cam.W, H = cam.H;
+    const int tile = walk_tile_of_wave<WPB>();
+    if (tile >= cam.gx * cam.gy) return;
+    const TileWalk t = walk_tile(tile, tile_start, cap, W, H, cam.gx);
+    const int lane = t.lane;
+    const unsigned r0 = t.r0, r1 = t.r1;
     if (r1 <= r0) return;
-    const int px0 = tx * GS2M_TILE + (lane & 7), py0 = ty * GS2M_TILE + (lane >> 3);
+    float4* sa = &s_a[t.wave][0];
+    float4* sb = &s_b[t.wave][0];
+    float2* sc = &s_c[t.wave][0];
+    float* sz = &s_z[DEPTH ? t.wave : 0][0];
     const size_t plane = (size_t)H * W;
-    float pxf[4], pyf[4], T[4], dp0[4], dp1[4], dp2[4];
+    float T[4], dp0[4], dp1[4], dp2[4];
     int ncontrib[4];     // list position (relative to r0) after the pixel's last contributor
     bool done[4];
     // DEPTH: walk 1 carries S, Z and the list position after the median contributor (0: none); walk 2 keeps gD / S in sS and
@@ -141,14 +125,11 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
     int medpos[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int x = px0 + 8 * (k & 1), y = py0 + 8 * (k >> 1);
-        const bool inside = x < W && y < H;
-        pxf[k] = (float)x;
-        pyf[k] = (float)y;
+        const bool inside = t.inside[k];
         T[k] = 1.0f;
         ncontrib[k] = 0;
         done[k] = !inside;
-        const size_t pix = (size_t)y * W + x;
+        const size_t pix = (size_t)t.y[k] * W + t.x[k];
         if constexpr (DEPTH) {
             const bool col = inside && dL_dpix != nullptr;
             dp0[k] = col ? dL_dpix[pix] : 0.0f;
@@ -162,28 +143,18 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
             dp2[k] = inside ? dL_dpix[2 * plane + pix] : 0.0f;
         }
     }
-    // the 64 instances [base, base + 64) of the list -> LDS (lane l stages instance base + l)
+    // the shared gather, extended by what walk 2 needs of an instance: its blue channel and its row
     auto stage = [&](const unsigned base) __attribute__((always_inline)) {
-        gs2m_wave_sync();   // the previous batch has been read by every lane
-        if (base + (unsigned)lane < r1) {
-            unsigned gid = (unsigned)(keys[base + lane] & 0xffffffffull);
-            const bool known = gid < (unsigned)P;   // never index the records with an id the forward cannot have written
-            gid = known ? gid : 0u;
-            const float4 ra = recs.ab[2 * (size_t)gid], rb = recs.ab[2 * (size_t)gid + 1], rc = recs.c[gid];
+        walk_gather<DEPTH>(t, base, keys, recs, P, sa, sb, sz, [&](const unsigned gid, const float4 rc) __attribute__((always_inline)) {
             const unsigned rect0 = __float_as_uint(rc.z), rect1 = __float_as_uint(rc.w);
             const int x0 = (int)(rect0 & 0xffffu), y0 = (int)(rect0 >> 16), x1 = (int)(rect1 & 0xffffu);
             // slot of this tile inside the Gaussian's tile rect (the lists only hold tiles of the rect)
-            const unsigned row = row_offset[gid] + (unsigned)((ty - y0) * (x1 - x0) + (tx - x0));
-            sa[lane] = ra;
-            sb[lane] = rb;
-            if (!known) sb[lane].y = 0.0f;   // opacity 0: alpha < 1/255 everywhere, the instance is skipped by both walks
+            const unsigned row = row_offset[gid] + (unsigned)((t.ty - y0) * (x1 - x0) + (t.tx - x0));
             float2 c;
             c.x = rc.x;
             c.y = __uint_as_float(row);
             sc[lane] = c;
-            if constexpr (DEPTH) sz[lane] = rc.y;
-        }
-        gs2m_wave_sync();
+        });
     };
     // ---- walk 1, front to back: T_final and n_contrib of every pixel (forward.cu:324-357)
     for (unsigned base = r0; base < r1; base += 64u) {
@@ -194,24 +165,10 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
             const float4 A = sa[j], B = sb[j];
             float z = 0.0f;
             if constexpr (DEPTH) z = sz[j];
+            const int pos = (int)(base - r0) + j + 1;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float dx, dy, G, alpha;
-                const bool ok = bw_alpha(A, B, pxf[k], pyf[k], dx, dy, G, alpha) && !done[k];
-                const float test_T = T[k] * (1.0f - alpha);
-                const bool sat = ok && test_T < 0.0001f;     // stop BEFORE accumulating (forward.cu:345-350)
-                done[k] = done[k] || sat;
-                if (ok && !sat) {
-                    if constexpr (DEPTH) {   // k_blend_depth's own operations: D below has the forward's bits
-                        const float w = alpha * T[k];
-                        sS[k] += w;
-                        sZ[k] = fmaf(w, z, sZ[k]);
-                        if (medpos[k] == 0 && test_T <= 0.5f) medpos[k] = (int)(base - r0) + j + 1;
-                    }
-                    T[k] = test_T;
-                    ncontrib[k] = (int)(base - r0) + j + 1;
-                }
-            }
+            for (int k = 0; k < 4; ++k)   // DEPTH = false: sS, sZ and medpos are not initialised, and walk_step does not touch them
+                walk_step<DEPTH, true>(A, B, z, t.pxf[k], t.pyf[k], T[k], done[k], sS[k], sZ[k], medpos[k], pos, &ncontrib[k], pos);
         }
     }
     int nmax = ncontrib[0] > ncontrib[1] ? ncontrib[0] : ncontrib[1];
@@ -242,7 +199,7 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
         for (int k = 0; k < 4; ++k) {
             // a pixel with a contributor lies inside the image and has S > 0 (alpha >= 1/255, T >= 1e-4); the others add nothing
             const bool live = ncontrib[k] > 0;
-            const size_t pix = (size_t)(py0 + 8 * (k >> 1)) * W + (size_t)(px0 + 8 * (k & 1));
+            const size_t pix = (size_t)t.y[k] * W + (size_t)t.x[k];
             const float S = sS[k];
             const float gD = (live && dg.dL_ddepth) ? dg.dL_ddepth[pix] : 0.0f;
             gM[k] = (live && dg.dL_dmedian) ? dg.dL_dmedian[pix] : 0.0f;
@@ -271,7 +228,7 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float dx, dy, G, alpha;
-                const bool ok = bw_alpha(A, B, pxf[k], pyf[k], dx, dy, G, alpha) && idx < ncontrib[k];
+                const bool ok = bw_alpha(A, B, t.pxf[k], t.pyf[k], dx, dy, G, alpha) && idx < ncontrib[k];
                 if (ok) {
                     any = true;
                     T[k] = T[k] / (1.0f - alpha);

@@ -87,7 +87,6 @@ def _rasterize_no_grad(means3D, sh, colors_precomp, opacities, scales, rotations
         raise RuntimeError("means3D must have dimensions (num_points, 3)")   # rasterize_points.cu:57-59
     rs = raster_settings
     h = _handle(means3D.device)
-    none_if_empty = _none_if_empty
     if rs.debug:
         # the reference's debug mode (DGR __init__.py:83-90): keep a host copy of every argument and, if the rasteriser
         # fails, leave it in snapshot_fw.dump for post-mortem; the C ABI call itself runs with a sync + check per launch
@@ -96,130 +95,117 @@ def _rasterize_no_grad(means3D, sh, colors_precomp, opacities, scales, rotations
             rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, rs.campos,
             rs.prefiltered, rs.debug))
         try:
-            return _forward(h, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, none_if_empty)
+            return _forward(h, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         except Exception as ex:
             torch.save(keep, "snapshot_fw.dump")
             print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
             raise ex
-    return _forward(h, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, none_if_empty)
+    return _forward(h, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
 
 
-def _forward(h, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, none_if_empty):
-    color, radii = h.forward(
-        _f32c(means3D), _f32c(opacities).reshape(-1), _f32c(rs.viewmatrix), _f32c(rs.projmatrix), _f32c(rs.campos),
-        _f32c(rs.bg), int(rs.image_width), int(rs.image_height), float(rs.tanfovx), float(rs.tanfovy),
-        shs=none_if_empty(sh), colors_precomp=none_if_empty(colors_precomp), scales=none_if_empty(scales),
-        rotations=none_if_empty(rotations), cov3D_precomp=none_if_empty(cov3Ds_precomp),
-        sh_degree=int(rs.sh_degree), scale_modifier=float(rs.scale_modifier), prefiltered=bool(rs.prefiltered),
-        debug=bool(rs.debug))
-    return color, radii
+def _call_args(rs, sh, colors_precomp, scales, rotations, cov3Ds_precomp):
+    """What ``Rasterizer.forward`` and ``.backward`` both take after the per-Gaussian leading arguments: the camera tuple and
+    the keyword arguments (an empty tensor = not given)."""
+    cam = (_f32c(rs.viewmatrix), _f32c(rs.projmatrix), _f32c(rs.campos), _f32c(rs.bg), int(rs.image_width),
+           int(rs.image_height), float(rs.tanfovx), float(rs.tanfovy))
+    args = dict(shs=_none_if_empty(sh), colors_precomp=_none_if_empty(colors_precomp), scales=_none_if_empty(scales),
+                rotations=_none_if_empty(rotations), cov3D_precomp=_none_if_empty(cov3Ds_precomp), sh_degree=int(rs.sh_degree),
+                scale_modifier=float(rs.scale_modifier), debug=bool(rs.debug))
+    return cam, args
+
+
+def _forward(h, rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+    cam, args = _call_args(rs, sh, colors_precomp, scales, rotations, cov3Ds_precomp)
+    return h.forward(_f32c(means3D), _f32c(opacities).reshape(-1), *cam, prefiltered=bool(rs.prefiltered), **args)
+
+
+def _function_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+    """Forward of both autograd Functions: the plain forward, and in ``ctx`` the inputs, the handle and the handle's call count
+    (the reference keeps its three byte arenas in ``ctx``; here the forward state lives in the per-device handle)."""
+    color, radii = _rasterize_no_grad(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+    h = _handle(means3D.device)
+    ctx.raster_settings = raster_settings
+    ctx.handle = h
+    ctx.state_calls = h.state_calls
+    ctx.opacity_shape = tuple(opacities.shape)
+    ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities)
+    ctx.mark_non_differentiable(radii)
+    return h, color, radii
+
+
+def _function_backward(ctx, grad_color, **map_grads):
+    """Backward of both autograd Functions: one ``Rasterizer.backward`` call with the upstream gradient of the image and, for the
+    depth Function, of the maps (``grad_depth`` / ``grad_median`` / ``grad_alpha``).  If another forward (or ``render_views``)
+    has overwritten the handle's state since ours -- two forwards before one backward, several views per optimiser step, another
+    user of the handle -- ours is replayed first into a scratch image.  With ``raster_settings.debug`` a failure leaves the
+    arguments in ``snapshot_bw.dump`` (the reference's debug mode, DGR __init__.py:118-132), for the depth Function too.
+    -> the nine gradients of DGR __init__.py:143-153."""
+    rs = ctx.raster_settings
+    h = ctx.handle
+    colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities = ctx.saved_tensors
+    cam, args = _call_args(rs, sh, colors_precomp, scales, rotations, cov3Ds_precomp)
+    opt = lambda t: None if t is None else _f32c(t)   # an output the loss does not use: a NULL map
+
+    def run():
+        if h.state_calls != ctx.state_calls:
+            h.forward(_f32c(means3D), _f32c(opacities).reshape(-1), *cam, prefiltered=bool(rs.prefiltered), **args)
+            ctx.state_calls = h.state_calls
+        return h.backward(opt(grad_color), _f32c(means3D), *cam, **{k: opt(v) for k, v in map_grads.items()}, **args)
+
+    if rs.debug:
+        keep = tuple(t.detach().cpu().clone() if isinstance(t, torch.Tensor) else t for t in (
+            rs.bg, means3D, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+            rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, sh, rs.sh_degree, rs.campos, rs.debug))
+        try:
+            g = run()
+        except Exception as ex:
+            torch.save(keep, "snapshot_bw.dump")
+            print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+            raise ex
+    else:
+        g = run()
+    given = lambda t: t is not None and t.numel() > 0
+    # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings
+    return (g["mean3D"], g["mean2D"], g["sh"] if given(sh) else None, g["color"] if given(colors_precomp) else None,
+            g["opacity"].reshape(ctx.opacity_shape), g["scale"] if given(scales) else None,
+            g["rot"] if given(rotations) else None, g["cov3D"] if given(cov3Ds_precomp) else None, None)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
-    """DGR __init__.py:44-155.  The reference keeps its three byte arenas in ``ctx``; here the forward state lives in the
-    per-device handle, and ``ctx`` keeps the inputs and the handle's call count."""
+    """DGR __init__.py:44-155: ``(color, radii)`` out, nine gradients back (``_function_forward`` / ``_function_backward``)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        color, radii = _rasterize_no_grad(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                          raster_settings)
-        h = _handle(means3D.device)
-        ctx.raster_settings = raster_settings
-        ctx.handle = h
-        ctx.state_calls = h.state_calls
-        ctx.opacity_shape = tuple(opacities.shape)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities)
-        ctx.mark_non_differentiable(radii)
+        _, color, radii = _function_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                            raster_settings)
         return color, radii
 
     @staticmethod
     def backward(ctx, grad_out_color, _):
-        rs = ctx.raster_settings
-        h = ctx.handle
-        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities = ctx.saved_tensors
-        args = dict(shs=_none_if_empty(sh), colors_precomp=_none_if_empty(colors_precomp), scales=_none_if_empty(scales),
-                    rotations=_none_if_empty(rotations), cov3D_precomp=_none_if_empty(cov3Ds_precomp), sh_degree=int(rs.sh_degree),
-                    scale_modifier=float(rs.scale_modifier), debug=bool(rs.debug))
-        cam = (_f32c(rs.viewmatrix), _f32c(rs.projmatrix), _f32c(rs.campos), _f32c(rs.bg), int(rs.image_width),
-               int(rs.image_height), float(rs.tanfovx), float(rs.tanfovy))
-
-        def run():
-            if h.state_calls != ctx.state_calls:
-                # another forward (or render_views) has overwritten the handle's state since ours: replay ours into a scratch
-                # image (two forwards before one backward, several views per optimiser step, another user of the handle)
-                h.forward(_f32c(means3D), _f32c(opacities).reshape(-1), *cam, prefiltered=bool(rs.prefiltered), **args)
-                ctx.state_calls = h.state_calls
-            return h.backward(_f32c(grad_out_color), _f32c(means3D), *cam, **args)
-
-        if rs.debug:
-            keep = tuple(t.detach().cpu().clone() if isinstance(t, torch.Tensor) else t for t in (
-                rs.bg, means3D, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
-                rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, rs.debug))
-            try:
-                g = run()
-            except Exception as ex:
-                torch.save(keep, "snapshot_bw.dump")
-                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                raise ex
-        else:
-            g = run()
-        given = lambda t: t is not None and t.numel() > 0
-        # DGR __init__.py:143-153: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings
-        return (g["mean3D"], g["mean2D"], g["sh"] if given(sh) else None, g["color"] if given(colors_precomp) else None,
-                g["opacity"].reshape(ctx.opacity_shape), g["scale"] if given(scales) else None,
-                g["rot"] if given(rotations) else None, g["cov3D"] if given(cov3Ds_precomp) else None, None)
-
-
-def _backward_args(ctx):
-    rs = ctx.raster_settings
-    colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities = ctx.saved_tensors
-    args = dict(shs=_none_if_empty(sh), colors_precomp=_none_if_empty(colors_precomp), scales=_none_if_empty(scales),
-                rotations=_none_if_empty(rotations), cov3D_precomp=_none_if_empty(cov3Ds_precomp), sh_degree=int(rs.sh_degree),
-                scale_modifier=float(rs.scale_modifier), debug=bool(rs.debug))
-    cam = (_f32c(rs.viewmatrix), _f32c(rs.projmatrix), _f32c(rs.campos), _f32c(rs.bg), int(rs.image_width),
-           int(rs.image_height), float(rs.tanfovx), float(rs.tanfovy))
-    return args, cam
+        return _function_backward(ctx, grad_out_color)
 
 
 class _RasterizeGaussiansDepth(torch.autograd.Function):
     """``_RasterizeGaussians`` with the depth and opacity maps as three more differentiable outputs (an extension).  The
     backward passes the four upstream gradients to one ``Rasterizer.backward`` call (``gs2m_rasterize_backward_depth``); an
-    output the loss does not use arrives as None and is passed as a NULL map.  It replays its forward when the handle's state
-    has moved on, exactly as the colour Function does."""
+    output the loss does not use arrives as None and is passed as a NULL map.  Everything else -- the replay when the handle's
+    state has moved on, the ``debug`` snapshot, the gradient tuple -- is the colour Function's, by the same code."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        color, radii = _rasterize_no_grad(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                          raster_settings)
-        h = _handle(means3D.device)
+        h, color, radii = _function_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                            raster_settings)
         maps = h.depth_maps(int(raster_settings.image_width), int(raster_settings.image_height), like=color)
-        ctx.raster_settings = raster_settings
-        ctx.handle = h
-        ctx.state_calls = h.state_calls
-        ctx.opacity_shape = tuple(opacities.shape)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities)
-        ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)
         return color, radii, maps["expected"], maps["median"], maps["alpha"]
 
     @staticmethod
     def backward(ctx, grad_color, _, grad_expected, grad_median, grad_alpha):
-        rs = ctx.raster_settings
-        h = ctx.handle
-        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities = ctx.saved_tensors
-        args, cam = _backward_args(ctx)
-        if h.state_calls != ctx.state_calls:
-            h.forward(_f32c(means3D), _f32c(opacities).reshape(-1), *cam, prefiltered=bool(rs.prefiltered), **args)
-            ctx.state_calls = h.state_calls
-        opt = lambda t: None if t is None else _f32c(t)
         if grad_color is None and grad_expected is None and grad_median is None and grad_alpha is None:
-            grad_color = torch.zeros((3, cam[5], cam[4]), dtype=torch.float32, device=means3D.device)
-        g = h.backward(opt(grad_color), _f32c(means3D), *cam, grad_depth=opt(grad_expected), grad_median=opt(grad_median),
-                       grad_alpha=opt(grad_alpha), **args)
-        given = lambda t: t is not None and t.numel() > 0
-        return (g["mean3D"], g["mean2D"], g["sh"] if given(sh) else None, g["color"] if given(colors_precomp) else None,
-                g["opacity"].reshape(ctx.opacity_shape), g["scale"] if given(scales) else None,
-                g["rot"] if given(rotations) else None, g["cov3D"] if given(cov3Ds_precomp) else None, None)
+            rs = ctx.raster_settings
+            grad_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32,
+                                     device=ctx.saved_tensors[1].device)
+        return _function_backward(ctx, grad_color, grad_depth=grad_expected, grad_median=grad_median, grad_alpha=grad_alpha)
 
 
 class GaussianRasterizer(nn.Module):
@@ -259,23 +245,18 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = torch.Tensor([])
         # Invoke the HIP rasterization routine
-        if return_depth:
-            tensors = (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)
-            if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
-                out = _RasterizeGaussiansDepth.apply(*tensors, raster_settings)
-                h = _handle(means3D.device)
-                self._last = (h, h.state_calls, tensors[:1] + tensors[2:])
-                return out
-            color, radii = _rasterize_no_grad(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                              raster_settings)
-            h = _handle(means3D.device)
-            self._last = (h, h.state_calls, tensors[:1] + tensors[2:])
-            maps = self.depth_maps()
-            return color, radii, maps["expected"], maps["median"], maps["alpha"]
-        out = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                  cov3D_precomp, raster_settings)
+        tensors = (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)
+        with_graph = return_depth and torch.is_grad_enabled() and any(
+            isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+        if with_graph:
+            out = _RasterizeGaussiansDepth.apply(*tensors, raster_settings)
+        else:
+            out = rasterize_gaussians(*tensors, raster_settings)
         h = _handle(means3D.device)
-        self._last = (h, h.state_calls, (means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp))
+        self._last = (h, h.state_calls, tensors[:1] + tensors[2:])
+        if return_depth and not with_graph:
+            maps = self.depth_maps()
+            out = (*out, maps["expected"], maps["median"], maps["alpha"])
         return out
 
     def depth_maps(self, want=("expected", "median", "alpha")):
@@ -292,6 +273,6 @@ class GaussianRasterizer(nn.Module):
         with torch.no_grad():
             if h.state_calls != calls:
                 means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp = inputs
-                _forward(h, rs, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, _none_if_empty)
+                _forward(h, rs, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)
                 self._last = (h, h.state_calls, inputs)
             return h.depth_maps(int(rs.image_width), int(rs.image_height), want=want, like=_f32c(rs.bg))

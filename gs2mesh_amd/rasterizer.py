@@ -108,6 +108,13 @@ def morton_order(xyz, bits: int = 10):
     return np.ascontiguousarray(np.argsort(code, kind="stable").astype(np.int32))
 
 
+def _sh_count(shs) -> int:
+    """M of an operator-level ``shs`` [P,M,3] (torch or numpy); 0 when it is None or empty (colours are precomputed)."""
+    if shs is None or (hasattr(shs, "numel") and shs.numel() == 0) or getattr(shs, "size", 1) == 0:
+        return 0
+    return int(shs.shape[1])
+
+
 class Rasterizer:
     """Owns one ``gs2m_raster`` handle (persistent arenas).  Not thread-safe; one stream at a time."""
 
@@ -174,8 +181,7 @@ class Rasterizer:
         instance arena is checked after the call and the pass is repeated once if it overflowed."""
         P = int(means3D.shape[0])
         D = int(sh_degree)
-        M = 0 if shs is None or (hasattr(shs, "numel") and shs.numel() == 0) or getattr(shs, "size", 1) == 0 \
-            else int(shs.shape[1])
+        M = _sh_count(shs)
         self.state_calls += 1
         out = _empty(means3D, (3, int(H), int(W)), np.float32)
         radii = _empty(means3D, (P,), np.int32)
@@ -216,8 +222,7 @@ class Rasterizer:
         ``want_conic``.  Every array is written in full; synchronises the stream once."""
         P = int(means3D.shape[0])
         D = int(sh_degree)
-        M = 0 if shs is None or (hasattr(shs, "numel") and shs.numel() == 0) or getattr(shs, "size", 1) == 0 \
-            else int(shs.shape[1])
+        M = _sh_count(shs)
         st = _stream_of(means3D, stream)
         f32 = torch.float32 if _is_torch(means3D) else None
         g = dict(mean2D=_empty(means3D, (P, 3), np.float32), opacity=_empty(means3D, (P,), np.float32),

@@ -273,7 +273,7 @@ int gs2m_raster_backward_rows(gs2m_raster* r, int64_t* rows, int64_t* arena_byte
  * instance j of the tile's list in order:
  *     skip j if power > 0 or alpha < 1/255, with alpha = min(0.99, o G)
  *     T' = T (1 - alpha); if T' < 1e-4 the pixel is finished, BEFORE accumulating (forward.cu:345-350)
- *     w = alpha T;  S += w;  Z += w z_j;  T = T';   if med == 0 and T <= 0.5: med = z_j
+ *     S = fma(T, alpha, S);  w = alpha T (rounded);  Z = fma(w, z_j, Z);  T = T';   if med == 0 and T <= 0.5: med = z_j
  * z_j is the view-space z of the Gaussian's CENTRE (the depth of the sort key), not a ray-surface intersection.
  *
  *   depth_expected[H,W]  device or NULL: S > 0 ? Z / S : 0    (alpha-weighted mean z of the contributors)

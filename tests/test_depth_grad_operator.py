@@ -93,6 +93,36 @@ def test_a_loss_on_one_map_alone_reaches_the_inputs(dev):
     check("operator median alone", g, {k: g64[2][k] for k in g}, e32[2])
 
 
+def test_a_colour_only_loss_has_the_colour_functions_gradients_bit_for_bit(dev):
+    """operator-level twin of test_colour_only_call_is_the_colour_backward_bit_for_bit: with the maps ignored by the loss the
+    depth Function's backward is the colour Function's -- one shared body, the colour kernels.  200 Gaussians on a 33 x 17
+    image: 3 x 2 tiles, partial in both axes"""
+    from gs2mesh_amd.diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+    W, H, f = 33, 17, 30.0
+    g, s, q, o, shs, cam, _ = scene(200, 9, W, H, f, log_s=math.log(0.06))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
+    rs = GaussianRasterizationSettings(H, W, cam.tanfovx, cam.tanfovy, t(np.array([0.1, 0.2, 0.3])), 1.0,
+                                       t(cam.world_view_transform), t(cam.full_proj_transform), 3, t(cam.camera_center), False, False)
+    w = t(np.random.default_rng(4).uniform(-1.0, 1.0, (3, H, W)))
+
+    def grads(**kw):
+        inp = dict(means3D=t(g["xyz"]), means2D=torch.zeros((200, 3), device=dev), opacities=t(o.reshape(-1, 1)), shs=t(shs),
+                   scales=t(s), rotations=t(q))
+        for v in inp.values():
+            v.requires_grad_(True)
+        outs = GaussianRasterizer(rs)(**inp, **kw)
+        (outs[0] * w).sum().backward()
+        return outs, {k: v.grad for k, v in inp.items()}
+
+    plain, g_colour = grads()
+    with_maps, g_depth = grads(return_depth=True)
+    assert len(plain) == 2 and len(with_maps) == 5 and torch.equal(plain[0], with_maps[0])
+    assert float((with_maps[4] > 0).float().mean()) > 0.3, "the scene covers the image"
+    for k in g_colour:
+        assert g_colour[k] is not None and float(g_colour[k].abs().max()) > 0, k
+        assert torch.equal(g_colour[k], g_depth[k]), k
+
+
 def test_backward_after_another_forward_replays_its_own(dev):
     from gs2mesh_amd.diff_gaussian_rasterization import GaussianRasterizer
     ca, cb = case("small800"), case("precomp")

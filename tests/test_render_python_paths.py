@@ -88,3 +88,50 @@ def test_debug_mode_leaves_a_snapshot_on_failure(monkeypatch, tmp_path):
         r2(means3D=torch.zeros(P, 3), means2D=torch.zeros(P, 3), opacities=torch.ones(P, 1), shs=torch.zeros(P, 16, 3),
            scales=torch.ones(P, 3), rotations=torch.ones(P, 4))
     assert not os.path.exists(tmp_path / "snapshot_fw.dump")
+
+
+@pytest.mark.parametrize("return_depth", [True, False], ids=["depth_function", "colour_function"])
+def test_debug_mode_leaves_a_backward_snapshot_on_failure(monkeypatch, tmp_path, return_depth):
+    """the backward twin (DGR __init__.py:118-132): both autograd Functions go through one backward, so the depth Function
+    writes snapshot_bw.dump as well, in the colour Function's layout"""
+    import gs2mesh_amd.diff_gaussian_rasterization as dgr
+    P, W, H = 5, 32, 24
+
+    class ForwardOnly:
+        state_calls = 0
+
+        def forward(self, means3D, *a, **k):
+            return torch.zeros(3, H, W), torch.zeros(P, dtype=torch.int32)
+
+        def depth_maps(self, width, height, want=("expected", "median", "alpha"), like=None):
+            return {k: torch.zeros(height, width) for k in want}
+
+        def backward(self, *a, **k):
+            raise RuntimeError("simulated device failure")
+
+    h = ForwardOnly()
+    monkeypatch.setattr(dgr, "_handle", lambda device: h)
+    monkeypatch.chdir(tmp_path)
+    rs = dgr.GaussianRasterizationSettings(H, W, 0.5, 0.5, torch.zeros(3), 1.0, torch.eye(4), torch.eye(4), 3, torch.zeros(3),
+                                          False, True)
+
+    def run(settings):
+        inp = dict(means3D=torch.zeros(P, 3, requires_grad=True), means2D=torch.zeros(P, 3), opacities=torch.ones(P, 1),
+                   shs=torch.zeros(P, 16, 3), scales=torch.ones(P, 3), rotations=torch.ones(P, 4))
+        outs = dgr.GaussianRasterizer(settings)(**inp, return_depth=return_depth)
+        assert len(outs) == (5 if return_depth else 2)
+        loss = outs[0].sum() + (outs[2].sum() if return_depth else 0.0)
+        with pytest.raises(RuntimeError, match="simulated device failure"):
+            loss.backward()
+
+    run(rs)
+    snap = torch.load(tmp_path / "snapshot_bw.dump", weights_only=False)
+    # bg, means3D, colors_precomp, scales, rotations, scale_modifier, cov3Ds_precomp, viewmatrix, projmatrix, tanfovx, tanfovy,
+    # grad_out_color, sh, sh_degree, campos, debug
+    assert len(snap) == 16 and snap[1].shape == (P, 3) and snap[2].numel() == 0 and snap[3].shape == (P, 3)
+    assert snap[11].shape == (3, H, W) and bool((snap[11] == 1).all()) and snap[12].shape == (P, 16, 3)
+    assert snap[13] == 3 and snap[15] is True
+    # without debug: no dump
+    os.remove(tmp_path / "snapshot_bw.dump")
+    run(rs._replace(debug=False))
+    assert not os.path.exists(tmp_path / "snapshot_bw.dump")
