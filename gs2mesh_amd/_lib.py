@@ -62,6 +62,7 @@ BLEND_PROF_COUNTERS = ("waves", "wave_cycles", "dma_wait", "staging", "prefetch_
 XFORM_SUM_F32, XFORM_RAW_F32, XFORM_SUM_PACKED = 0, 1, 2
 XFORM_PACKED_MAX_FRAMES = 1023
 MESH_SAMPLE_CAP, MESH_SAMPLE_TOTAL, MESH_SAMPLE_INDEX = 1, 2, 4     # status bits of gs2m_mesh_sample_count
+ICP_SUMS = 18                                                       # 8-byte slots gs2m_icp_step writes
 OPT_DEBUG_SYNC = 3
 OPT_STAGE_TIMING = 4
 RASTER_STAGES = ("project", "hist_colscan", "tile_scan", "scatter", "sort_tiles", "blend", "count_tiles")
@@ -103,6 +104,10 @@ _PROTOS = {
     "gs2m_knn_mean_dist2": (i32, [i32, vp, vp, vp, i64, vp, vp]),
     "gs2m_nn_scratch_bytes": (i64, [i32, i32]),
     "gs2m_nn_dist2": (i32, [i32, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp]),
+    "gs2m_icp_scratch_bytes": (i64, [i32, i32]),
+    "gs2m_icp_prepare": (i32, [i32, vp, vp, vp, vp, i64, vp]),
+    "gs2m_icp_step": (i32, [i32, vp, vp, vp, i32, vp, vp, f64, vp, i64, vp, vp, vp, vp]),
+    "gs2m_voxel_mean": (i32, [i32, vp, vp, i32, vp, vp, vp]),
     "gs2m_mesh_sample_count": (i32, [i64, vp, i64, vp, f64, vp, vp, vp, i64, vp, C.POINTER(i64), C.POINTER(C.c_uint32)]),
     "gs2m_mesh_sample_emit": (i32, [i64, vp, i64, vp, f64, vp, vp, i64, vp, vp]),
     "gs2m_points_cull_views": (i32, [i32, vp, i32, vp, vp, i32, i32, f32, f32, vp, vp]),

@@ -45,23 +45,14 @@ GS2M_DEVICE float nn_box_box_dist2(const float lo[3], const float hi[3], const f
     return (dx * dx + dy * dy) + dz * dz;
 }
 
-// Pass 2.  Waves are independent (no workgroup barrier): KNN_WAVES of them share a workgroup only to fill a CU.
-// groups = supers = 0 (no references) writes (+inf, -1).
-GS2M_KERNEL void __launch_bounds__(64 * KNN_WAVES)
-k_nn_search(int Q, const float* __restrict__ queries, const int* __restrict__ query_order, int R, int groups, int supers,
-            const float4* __restrict__ rec, const float4* __restrict__ box, const float4* __restrict__ sbox,
-            float* __restrict__ out_d2, int* __restrict__ out_idx) {
-    __shared__ float4 tiles[KNN_WAVES][KNN_GROUP];
-    const int lane = gs2m_lane(), wave = (int)(threadIdx.x >> 6);
-    float4* tile = tiles[wave];
-    const int64_t q0 = ((int64_t)blockIdx.x * KNN_WAVES + wave) * 64;
-    if (q0 >= Q) return;                                              // whole wave: no collective is left half-attended
-    const int64_t pos = q0 + lane < Q ? q0 + lane : (int64_t)Q - 1;
-    const bool stored = q0 + lane < Q;
-    int id = query_order ? query_order[pos] : (int)pos;
-    if ((unsigned)id >= (unsigned)Q) id = (int)pos;
-    const float px = queries[3 * (size_t)id], py = queries[3 * (size_t)id + 1], pz = queries[3 * (size_t)id + 2];
-    const bool live = stored && px == px && py == py && pz == pz;   // a NaN query asks for nothing and finds nothing
+// The walk of one wave: lane l's query is (px, py, pz), `live` where the lane has a query without a NaN coordinate (a NaN query
+// asks for nothing and finds nothing); -> the lane's best key.  Called by every lane of the wave (it holds wave collectives);
+// `tile` is the wave's own KNN_GROUP records of LDS.  The one walk of the library: k_nn_search and the ICP step
+// (icp_kernels.h), which differ only in where a query comes from, both call it.
+GS2M_DEVICE unsigned long long nn_search_wave(float px, float py, float pz, bool live, float4* tile, int R, int groups, int supers,
+                                              const float4* __restrict__ rec, const float4* __restrict__ box,
+                                              const float4* __restrict__ sbox) {
+    const int lane = gs2m_lane();
     unsigned long long best = NN_NONE;
     if (supers > 0) {
         // the box of the wave's queries, then the nearest super-box and the nearest group in it
@@ -118,6 +109,26 @@ k_nn_search(int Q, const float* __restrict__ queries, const int* __restrict__ qu
             }
         }
     }
+    return best;
+}
+
+// Pass 2.  Waves are independent (no workgroup barrier): KNN_WAVES of them share a workgroup only to fill a CU.
+// groups = supers = 0 (no references) writes (+inf, -1).
+GS2M_KERNEL void __launch_bounds__(64 * KNN_WAVES)
+k_nn_search(int Q, const float* __restrict__ queries, const int* __restrict__ query_order, int R, int groups, int supers,
+            const float4* __restrict__ rec, const float4* __restrict__ box, const float4* __restrict__ sbox,
+            float* __restrict__ out_d2, int* __restrict__ out_idx) {
+    __shared__ float4 tiles[KNN_WAVES][KNN_GROUP];
+    const int lane = gs2m_lane(), wave = (int)(threadIdx.x >> 6);
+    const int64_t q0 = ((int64_t)blockIdx.x * KNN_WAVES + wave) * 64;
+    if (q0 >= Q) return;                                              // whole wave: no collective is left half-attended
+    const int64_t pos = q0 + lane < Q ? q0 + lane : (int64_t)Q - 1;
+    const bool stored = q0 + lane < Q;
+    int id = query_order ? query_order[pos] : (int)pos;
+    if ((unsigned)id >= (unsigned)Q) id = (int)pos;
+    const float px = queries[3 * (size_t)id], py = queries[3 * (size_t)id + 1], pz = queries[3 * (size_t)id + 2];
+    const bool live = stored && px == px && py == py && pz == pz;   // a NaN query asks for nothing and finds nothing
+    const unsigned long long best = nn_search_wave(px, py, pz, live, tiles[wave], R, groups, supers, rec, box, sbox);
     if (stored) {
         out_d2[id] = __uint_as_float((unsigned)(best >> 32));
         if (out_idx) out_idx[id] = (int)(unsigned)best;

@@ -4,6 +4,7 @@
 //   nn_kernels.h           gs2m_nn_*           nearest reference of every query (mesh evaluation); shares knn_scratch_layout
 //   mesh_sample_kernels.h  gs2m_mesh_sample_*  points on the surface of a triangle mesh (mesh evaluation)
 //   points_cull_kernels.h  gs2m_points_cull_views  keep-mask of a point set against the masks of all views (DTU's cull_scan)
+//   icp_kernels.h          gs2m_icp_*, gs2m_voxel_mean  one ICP iteration on f64 point sets over nn_kernels.h's walk; voxel means
 #include <math.h>
 #include <string.h>
 
@@ -13,6 +14,7 @@
 #include "nn_kernels.h"
 #include "mesh_sample_kernels.h"
 #include "points_cull_kernels.h"
+#include "icp_kernels.h"
 #include "api_check.h"
 #include "tsdf_internal.h"          // gs2m_launch_scan_u32
 
@@ -62,6 +64,65 @@ extern "C" int gs2m_nn_dist2(int Q, const float* queries, const int32_t* query_o
     }
     nn_launch((hipStream_t)stream, Q, queries, query_order, R, refs, ref_order, knn_scratch_layout(R > 0 ? scratch : nullptr, R), out_d2,
               out_idx);
+    return 0;
+}
+
+extern "C" int64_t gs2m_icp_scratch_bytes(int N, int R) { return icp_scratch_layout(nullptr, N, R).bytes; }
+
+extern "C" int gs2m_icp_prepare(int R, const double* target, const double* origin, const int32_t* ref_order, void* scratch,
+                                int64_t scratch_bytes, gs2m_stream stream) {
+    if (R < 0) {
+        gs2m_set_error("gs2m_icp_prepare: R = %d", R);
+        return 1;
+    }
+    if (R == 0) return 0;
+    if (!target || !origin) {
+        gs2m_set_error("gs2m_icp_prepare: NULL target or origin with R = %d", R);
+        return 1;
+    }
+    if (gs2m_scratch_refused("gs2m_icp_prepare", "gs2m_icp_scratch_bytes", scratch, scratch_bytes, gs2m_icp_scratch_bytes(0, R), 16))
+        return 1;
+    icp_prepare_launch((hipStream_t)stream, R, target, origin, ref_order, icp_scratch_layout(scratch, 0, R));
+    return 0;
+}
+
+extern "C" int gs2m_icp_step(int N, const double* source, const int32_t* query_order, const double* transform, int R,
+                             const double* target, const double* origin, double max_dist, void* scratch, int64_t scratch_bytes,
+                             void* sums, int32_t* out_idx, double* out_d2, gs2m_stream stream) {
+    if (N < 0 || R < 0) {
+        gs2m_set_error("gs2m_icp_step: N = %d, R = %d", N, R);
+        return 1;
+    }
+    if (!(max_dist > 0.0) || !(max_dist < INFINITY)) {
+        gs2m_set_error("gs2m_icp_step: max_dist = %g (must be positive and finite)", max_dist);
+        return 1;
+    }
+    if (!transform || !origin || !sums || (N > 0 && !source) || (N > 0 && R > 0 && !target)) {
+        gs2m_set_error("gs2m_icp_step: NULL transform, origin, sums, source or target with N = %d, R = %d", N, R);
+        return 1;
+    }
+    if (N > 0 && gs2m_scratch_refused("gs2m_icp_step", "gs2m_icp_scratch_bytes", scratch, scratch_bytes, gs2m_icp_scratch_bytes(N, R), 16))
+        return 1;
+    IcpXform x;
+    memcpy(x.t, transform, sizeof(x.t));
+    memcpy(x.o, origin, sizeof(x.o));
+    icp_step_launch((hipStream_t)stream, N, source, query_order, x, R, target, max_dist * max_dist, icp_scratch_layout(scratch, N, R),
+                    (double*)sums, out_idx, out_d2);
+    return 0;
+}
+
+extern "C" int gs2m_voxel_mean(int N, const double* points, const int32_t* order, int S, const int32_t* heads, double* means,
+                               gs2m_stream stream) {
+    if (N < 0 || S < 0) {
+        gs2m_set_error("gs2m_voxel_mean: N = %d, S = %d", N, S);
+        return 1;
+    }
+    if (S == 0) return 0;
+    if (!heads || !means || (N > 0 && (!points || !order))) {
+        gs2m_set_error("gs2m_voxel_mean: NULL points, order, heads or means with N = %d, S = %d", N, S);
+        return 1;
+    }
+    GS2M_LAUNCH(k_voxel_mean, dim3(((unsigned)S + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, N, points, order, S, heads, means);
     return 0;
 }
 

@@ -22,7 +22,16 @@ truth's bounding box, ``(gt.min(0) + gt.max(0)) / 2``, which keeps the f32 coord
 (spacing E * 2^-25: 2e-5 mm on a 600 mm DTU scan).  Distances are ``sqrt`` in f64 of the f32 squared distance, means are f64
 sums on the device.
 
-Outside this module, as in DESIGN.md: TNT's registration and cropping, MobileBrick's ICP, Poisson-disk sampling.
+Registration.  MobileBrick and TNT align the prediction to the ground truth with Open3D's ``registration_icp`` before they
+score it (evaluation/MobileBrick/eval_code/evaluate.py:82-93; evaluation/TNT/eval_code/python_toolbox/evaluation/run.py:92-124,
+registration.py:106-195, evaluation.py:60-88).  ``registration_icp`` is that loop on ``gs2m_icp_prepare`` / ``gs2m_icp_step``
+(the target's search structure built once, one kernel pass and one 144-byte copy per iteration) with ``umeyama`` on the host;
+``voxel_down_sample`` (``gs2m_voxel_mean``), ``uniform_down_sample`` and ``crop_points`` restate the Open3D calls around it,
+``mobilebrick_align``, ``tnt_register`` and ``tnt_evaluate`` the reference's flows.  Open3D's source was not at hand: its keep
+rule (strict ``<``), voxel key and polygon test are written as remembered, and say so where they stand.
+
+Outside this module, as in DESIGN.md: TNT's RANSAC trajectory alignment (``init_trans`` is an input; ``umeyama(...,
+with_scaling=True)`` on matched camera centres is the stand-in), normals, plots and coloured clouds, Poisson-disk sampling.
 """
 from __future__ import annotations
 
@@ -442,3 +451,308 @@ def evaluate_mesh(mesh, gt_points, density=0.2, max_dist=20, thresholds=(), obs_
     if n_culled is not None:
         out["n_vertices_culled"] = n_culled
     return out
+
+
+# ---- registration: Umeyama, the ICP loop, and the Open3D calls around it ---------------------------------------------------
+
+class RegistrationResult:
+    """What Open3D's ``RegistrationResult`` holds, plus the number of updates made."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, n_iterations, correspondence_set=None):
+        self.transformation = transformation
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.n_iterations = n_iterations
+        self.correspondence_set = correspondence_set
+
+    def __repr__(self):
+        return f"RegistrationResult(fitness={self.fitness:.6g}, inlier_rmse={self.inlier_rmse:.6g}, n_iterations={self.n_iterations})"
+
+
+def _umeyama_solve(cov, mu_s, mu_d, var_s, with_scaling):
+    """Eigen's ``umeyama`` from the centred covariance (1/n) sum (d - mu_d)(s - mu_s)^T, the means and the source variance"""
+    U, D, Vt = np.linalg.svd(cov)
+    S = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2] = -1.0
+    R = U @ np.diag(S) @ Vt
+    c = float((D * S).sum() / var_s) if with_scaling and var_s > 0 else 1.0
+    T = np.eye(4)
+    T[:3, :3] = c * R
+    T[:3, 3] = mu_d - c * (R @ mu_s)
+    return T
+
+
+def umeyama(src, dst, with_scaling=False):
+    """The least-squares similarity (or rigid) transform dst ~ c R src + t of matched rows -> 4 x 4 f64, numpy on the host, in
+    Eigen's formulation (``Eigen::umeyama``, which Open3D's ``TransformationEstimationPointToPoint`` calls): centred covariance
+    ``Sigma = (1/n) sum (d - mu_d)(s - mu_s)^T = U D V^T``, ``S = diag(1, 1, sign(det U det V))``, ``R = U S V^T``,
+    ``c = tr(D S) / sigma_s^2`` (1 without scaling), ``t = mu_d - c R mu_s``.  No rows give the identity."""
+    s = np.asarray(src, np.float64).reshape(-1, 3)
+    d = np.asarray(dst, np.float64).reshape(-1, 3)
+    if s.shape != d.shape:
+        raise ValueError(f"umeyama: {s.shape[0]} source rows, {d.shape[0]} destination rows")
+    n = s.shape[0]
+    if n == 0:
+        return np.eye(4)
+    mu_s, mu_d = s.mean(axis=0), d.mean(axis=0)
+    sc, dc = s - mu_s, d - mu_d
+    return _umeyama_solve(dc.T @ sc / n, mu_s, mu_d, float((sc * sc).sum() / n), with_scaling)
+
+
+def umeyama_from_moments(n, sum_p, sum_q, sum_pq, sum_pp, origin=(0.0, 0.0, 0.0), with_scaling=False):
+    """``umeyama`` from the sums of ``gs2m_icp_step`` over its n kept pairs: ``sum_p`` = sum p', ``sum_q`` = sum q',
+    ``sum_pq[a][b]`` = sum p'_a q'_b, ``sum_pp`` = sum |p'|^2, with p' = p - origin and q' = q - origin.  The covariance is
+    ``sum_pq^T / n - mu_q mu_p^T`` and the variance ``sum_pp / n - |mu_p|^2``: raw moments, which cancel like (extent of the
+    shifted coordinates / spread of the pairs)^2 -- the reason the kernel shifts by an origin inside the scene.  n = 0 gives the
+    identity."""
+    n = int(n)
+    if n == 0:
+        return np.eye(4)
+    o = np.asarray(origin, np.float64).reshape(3)
+    mu_s = np.asarray(sum_p, np.float64).reshape(3) / n
+    mu_d = np.asarray(sum_q, np.float64).reshape(3) / n
+    cov = np.asarray(sum_pq, np.float64).reshape(3, 3).T / n - np.outer(mu_d, mu_s)
+    var_s = float(sum_pp) / n - float(mu_s @ mu_s)
+    T = _umeyama_solve(cov, mu_s, mu_d, var_s, with_scaling)
+    T[:3, 3] = (T[:3, 3] + o) - T[:3, :3] @ o                        # from the shifted frame back to the caller's
+    return T
+
+
+def icp_loop(step, n_source, init=None, with_scaling=False, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30,
+             origin=(0.0, 0.0, 0.0)):
+    """Open3D's ``RegistrationICP`` loop over ``step(T) -> (n, sums [17] f64)`` (the slots 1..17 of ``gs2m_icp_step``):
+    evaluate at ``init``; up to ``max_iteration`` times ``T = umeyama(pairs) @ T`` and evaluate again; stop once
+    ``|d fitness| < relative_fitness`` and ``|d rmse| < relative_rmse``.  ``fitness = n / n_source`` (0 for no source),
+    ``inlier_rmse = sqrt(sum d2 / n)``, 0 when n = 0.  -> (T, fitness, inlier_rmse, n_iterations).  ``registration_icp`` runs
+    it on the kernel; the tests run the same function on the numpy statement of the kernel."""
+    T = np.eye(4) if init is None else np.array(init, np.float64).reshape(4, 4)
+
+    def evaluate(T):
+        n, sums = step(T)
+        n = int(n)
+        return n, sums, (n / n_source if n_source else 0.0), (float(np.sqrt(sums[0] / n)) if n else 0.0)
+
+    n, sums, fitness, rmse = evaluate(T)
+    done = 0
+    for _ in range(int(max_iteration)):
+        update = umeyama_from_moments(n, sums[1:4], sums[4:7], sums[7:16], sums[16], origin, with_scaling)
+        T = update @ T
+        done += 1
+        before = (fitness, rmse)
+        n, sums, fitness, rmse = evaluate(T)
+        if abs(before[0] - fitness) < relative_fitness and abs(before[1] - rmse) < relative_rmse:
+            break
+    return T, fitness, rmse, done
+
+
+def registration_icp(source, target, max_correspondence_distance, init=None, with_scaling=False, relative_fitness=1e-6,
+                     relative_rmse=1e-6, max_iteration=30, origin=None, sort=True, want_correspondences=False, lib=None,
+                     device=None):
+    """Open3D's point-to-point ``registration_icp(source, target, max_correspondence_distance, init,
+    TransformationEstimationPointToPoint(with_scaling), ICPConvergenceCriteria(relative_fitness, relative_rmse,
+    max_iteration))`` -> ``RegistrationResult`` (``transformation`` 4 x 4 f64 numpy).  The loop is ``icp_loop``; an iteration
+    is one ``gs2m_icp_step`` (include/gs2mesh_amd.h: f64 transform, the exact f32 nearest neighbour of ``gs2m_nn_dist2``, the
+    f64 keep rule d2 < max^2, fixed-order f64 sums) and one copy of 144 bytes to the host; the target's search structure is
+    built once (``gs2m_icp_prepare``).
+
+    Differences from Open3D, on purpose: the kernel applies the accumulated ``T`` to the ORIGINAL source every iteration (Open3D
+    transforms its copy in place by every update, so its rounding compounds); the neighbour is the nearest in f32 coordinates
+    relative to ``origin`` (default: the midpoint of the target's box), so among targets closer together than f32 resolves
+    another one than Open3D's may pair -- its distance and the moments are still f64 of the f64 points.
+    ``want_correspondences`` adds ``correspondence_set`` [n,2] int64 (source index, target index) of the last evaluation.
+    ``sort``: Morton orders for both sides from 1024 points (the source's at ``init``); the speed only."""
+    torch = _torch()
+    lib = lib or _lib.get()
+    if not 0 < float(max_correspondence_distance) < float("inf"):
+        raise ValueError(f"registration_icp: max_correspondence_distance = {max_correspondence_distance}")
+    src = _points(source, torch.float64, "source", device)
+    tgt = _points(target, torch.float64, "target", src.device.index if src.is_cuda else device)
+    if tgt.device != src.device:
+        raise ValueError(f"registration_icp: source on {src.device}, target on {tgt.device}")
+    N, R = int(src.shape[0]), int(tgt.shape[0])
+    T0 = np.eye(4) if init is None else np.array(init, np.float64).reshape(4, 4)
+    o_t = _origin(tgt, origin)
+    o = np.ascontiguousarray(o_t.detach().cpu().numpy(), np.float64)
+    ro = morton_order((tgt - o_t).to(torch.float32)) if sort and R >= MORTON_MIN_N else None
+    qo = None
+    if sort and N >= MORTON_MIN_N:
+        M = torch.from_numpy(T0).to(src.device)
+        moved = src @ M[:3, :3].T + M[:3, 3] - o_t
+        qo = morton_order(torch.nan_to_num(moved).to(torch.float32))
+    need = int(lib.gs2m_icp_scratch_bytes(N, R))
+    scratch = torch.empty(((need + 15) // 16 * 2,), dtype=torch.int64, device=src.device) if need else None
+    nbytes = 0 if scratch is None else scratch.shape[0] * 8
+    sums = torch.zeros((_lib.ICP_SUMS,), dtype=torch.int64, device=src.device)
+    idx = torch.empty((N,), dtype=torch.int32, device=src.device) if want_correspondences else None
+    d2 = torch.empty((N,), dtype=torch.float64, device=src.device) if want_correspondences else None
+    stream = _stream_of(src, None)
+    o_ptr = o.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.gs2m_icp_prepare(R, _ptr(tgt), o_ptr, _ptr(ro, torch.int32, "ref_order"), _ptr(scratch), nbytes, stream), lib)
+
+    def step(T):
+        Th = np.ascontiguousarray(T, np.float64)
+        _lib.check(lib.gs2m_icp_step(N, _ptr(src), _ptr(qo, torch.int32, "query_order"), Th.ctypes.data_as(C.c_void_p), R, _ptr(tgt),
+                                     o_ptr, float(max_correspondence_distance), _ptr(scratch), nbytes, _ptr(sums), _ptr(idx),
+                                     _ptr(d2), stream), lib)
+        host = sums.cpu().numpy()                                     # the iteration's one copy; it waits for the step
+        return int(host[0]), host[1:].copy().view(np.float64)
+
+    T, fitness, rmse, done = icp_loop(step, N, T0, with_scaling, relative_fitness, relative_rmse, max_iteration, o)
+    pairs = None
+    if want_correspondences:
+        kept = (idx >= 0) & (d2 < float(max_correspondence_distance) * float(max_correspondence_distance))
+        i = torch.nonzero(kept).reshape(-1)
+        pairs = torch.stack([i, idx[i].to(torch.int64)], dim=1).cpu().numpy()
+    return RegistrationResult(T, fitness, rmse, done, pairs)
+
+
+def voxel_down_sample(points, voxel_size, lib=None):
+    """Open3D's ``PointCloud.voxel_down_sample`` for points alone -> [S,3] f64 on the points' device: voxel
+    ``floor((p - (min - voxel_size / 2)) / voxel_size)`` per axis in f64 (Open3D's key, as remembered), every occupied voxel's
+    mean with the rows added in ascending original index (``gs2m_voxel_mean``: the order of Open3D's ``AccumulatedPoint``,
+    so the means carry its bits).  The output is in ascending (i, j, k) of the voxel; Open3D's is the iteration order of an
+    ``unordered_map``, so there is no order to reproduce."""
+    torch = _torch()
+    lib = lib or _lib.get()
+    p = _points(points, torch.float64, "points")
+    n = int(p.shape[0])
+    if not float(voxel_size) > 0:
+        raise ValueError(f"voxel_down_sample: voxel_size = {voxel_size}")
+    if n == 0:
+        return p
+    if n > 2 ** 31 - 1:
+        raise ValueError(f"voxel_down_sample: {n} points, more than 2^31 - 1")
+    lo = p.amin(dim=0) - float(voxel_size) * 0.5
+    ijk = torch.floor((p - lo) / float(voxel_size)).to(torch.int64)
+    dims = (ijk.amax(dim=0) + 1).tolist()
+    if dims[0] * dims[1] * dims[2] < 2 ** 62:
+        key = (ijk[:, 0] * dims[1] + ijk[:, 1]) * dims[2] + ijk[:, 2]
+    else:
+        _, key = torch.unique(ijk, dim=0, return_inverse=True)           # rows sort lexicographically: the same order
+    key, order = torch.sort(key, stable=True)
+    head = torch.ones((n,), dtype=torch.bool, device=p.device)
+    head[1:] = key[1:] != key[:-1]
+    heads = torch.nonzero(head).reshape(-1).to(torch.int32).contiguous()
+    order = order.to(torch.int32).contiguous()
+    S = int(heads.shape[0])
+    means = torch.empty((S, 3), dtype=torch.float64, device=p.device)
+    _lib.check(lib.gs2m_voxel_mean(n, _ptr(p), _ptr(order), S, _ptr(heads), _ptr(means), _stream_of(p, None)), lib)
+    return means
+
+
+def uniform_down_sample(points, every_k):
+    """Open3D's ``uniform_down_sample``: the rows 0, k, 2k, ..."""
+    if int(every_k) < 1:
+        raise ValueError(f"uniform_down_sample: every_k = {every_k}")
+    return _points(points, _torch().float64, "points")[::int(every_k)].contiguous()
+
+
+def read_crop_volume(json_path):
+    """A ``SelectionPolygonVolume`` file (TNT's ``<scene>.json``) -> dict(orthogonal_axis "x" / "y" / "z", axis_min, axis_max,
+    bounding_polygon [M,3] f64)."""
+    import json
+    with open(json_path) as f:
+        d = json.load(f)
+    axis = str(d["orthogonal_axis"]).lower()
+    if axis not in ("x", "y", "z"):
+        raise ValueError(f"read_crop_volume: orthogonal_axis = {d['orthogonal_axis']!r}")
+    return {"orthogonal_axis": axis, "axis_min": float(d["axis_min"]), "axis_max": float(d["axis_max"]),
+            "bounding_polygon": np.asarray(d["bounding_polygon"], np.float64).reshape(-1, 3)}
+
+
+def crop_points(points, volume, return_mask=False):
+    """Open3D's ``SelectionPolygonVolume.crop_point_cloud`` for points alone, as remembered (``CropInPolygon``): with w the
+    orthogonal axis and (u, v) the other two in ascending order, a point stays iff ``axis_min <= p_w <= axis_max`` (both ends
+    inclusive) and the even-odd rule puts (p_u, p_v) inside ``bounding_polygon``: every edge (a, b) with
+    ``(p_v < a_v) != (p_v < b_v)`` is crossed at ``a_u + (p_v - a_v) / (b_v - a_v) * (b_u - a_u)``, and the point is inside
+    iff an odd number of crossings lie at u < p_u.  Torch ops, no kernel.  -> the kept rows, in order (or the bool mask)."""
+    torch = _torch()
+    p = _points(points, torch.float64, "points")
+    w = "xyz".index(str(volume["orthogonal_axis"]).lower())
+    u, v = [a for a in range(3) if a != w]
+    poly = np.asarray(volume["bounding_polygon"], np.float64).reshape(-1, 3)
+    keep = (p[:, w] >= float(volume["axis_min"])) & (p[:, w] <= float(volume["axis_max"]))
+    inside = torch.zeros_like(keep)
+    pu, pv = p[:, u], p[:, v]
+    for i in range(poly.shape[0]):
+        a, b = poly[i], poly[(i + 1) % poly.shape[0]]
+        if a[v] == b[v]:
+            continue                                                  # never crossed: (p_v < a_v) == (p_v < b_v)
+        crossed = (pv < float(a[v])) != (pv < float(b[v]))
+        node = float(a[u]) + (pv - float(a[v])) / float(b[v] - a[v]) * float(b[u] - a[u])
+        inside = inside ^ (crossed & (node < pu))
+    keep = keep & inside
+    return keep if return_mask else p[keep]
+
+
+def _apply(T, points):
+    torch = _torch()
+    M = torch.from_numpy(np.ascontiguousarray(T, np.float64).reshape(4, 4)).to(points.device)
+    return points @ M[:3, :3].T + M[:3, 3]
+
+
+def mobilebrick_align(pred_mesh, gt_mesh, threshold=0.02, max_iteration=10, min_fitness=0.99, lib=None, device=None):
+    """MobileBrick's alignment (evaluate.py:82-93) -> (mesh, result): ``registration_icp`` with the GT vertices as the source
+    and the predicted vertices as the target, rigid, from the identity; a copy of ``pred_mesh`` transformed by
+    ``inv(result.transformation)`` when ``result.fitness > min_fitness``, an untouched copy otherwise, as the reference has it."""
+    import copy
+    pred, gt = _as_mesh(pred_mesh), _as_mesh(gt_mesh)
+    result = registration_icp(gt.vertices, pred.vertices, threshold, max_iteration=max_iteration, lib=lib, device=device)
+    out = copy.deepcopy(pred)
+    if result.fitness > min_fitness:
+        out.transform(np.linalg.inv(result.transformation))
+    return out, result
+
+
+TNT_MAX_POINTS = 4e6        # registration.py:41
+
+
+def tnt_register(pred_points, gt_points, init_trans, crop_volume, tau, lib=None, device=None):
+    """TNT's three refinement stages (run.py:98-102, registration.py:106-195) -> (transformation 4 x 4, [the three results]).
+    Each stage moves the prediction by the transform so far, crops both clouds with ``crop_volume``, thins them, runs
+    ``registration_icp`` with scaling from the identity (relative criteria 1e-6, 20 iterations) and multiplies the result on:
+    voxel tau / threshold 80 tau, voxel tau / 2 / threshold 20 tau, then every k-th point with k = round(n / 4e6) where a
+    cloud has more than 4e6 points / threshold 2 tau.  ``init_trans`` is the reference's trajectory alignment, an input here."""
+    torch = _torch()
+    pred = _points(pred_points, torch.float64, "pred_points", device)
+    gt = _points(gt_points, torch.float64, "gt_points", pred.device.index if pred.is_cuda else device)
+    T = np.array(init_trans, np.float64).reshape(4, 4)
+    tau = float(tau)
+    gt_crop = crop_points(gt, crop_volume)
+
+    def thin(p, voxel):
+        if voxel is not None:
+            return voxel_down_sample(p, voxel, lib=lib)
+        n = int(p.shape[0])
+        return uniform_down_sample(p, int(round(n / TNT_MAX_POINTS))) if n > TNT_MAX_POINTS else p
+
+    results = []
+    for voxel, threshold in ((tau, 80 * tau), (tau / 2.0, 20 * tau), (None, 2 * tau)):
+        s = thin(crop_points(_apply(T, pred), crop_volume), voxel)
+        t = thin(gt_crop, voxel)
+        r = registration_icp(s, t, threshold, with_scaling=True, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=20,
+                             lib=lib)
+        T = r.transformation @ T
+        results.append(r)
+    return T, results
+
+
+def tnt_evaluate(pred_points, gt_points, init_trans, crop_volume, tau, sort=True, lib=None, device=None):
+    """TNT's evaluation of a point cloud (run.py:92-124, evaluation.py:60-88, 173-177): ``tnt_register``, then both clouds
+    cropped and voxel-down-sampled at tau / 2, ``precision`` = the share of prediction -> GT distances < tau, ``recall`` = the
+    share of GT -> prediction distances < tau, ``fscore`` their harmonic mean (0 where both are 0).  The distances go through
+    ``_distances`` like every other metric here.  -> {precision, recall, fscore, transformation, n_source, n_target}."""
+    torch = _torch()
+    pred = _points(pred_points, torch.float64, "pred_points", device)
+    gt = _points(gt_points, torch.float64, "gt_points", pred.device.index if pred.is_cuda else device)
+    tau = float(tau)
+    T, _ = tnt_register(pred, gt, init_trans, crop_volume, tau, lib=lib, device=device)
+    s = voxel_down_sample(crop_points(_apply(T, pred), crop_volume), tau / 2.0, lib=lib)
+    t = voxel_down_sample(crop_points(gt, crop_volume), tau / 2.0, lib=lib)
+    o = _origin(t, None)
+    share = lambda d: float((d < tau).sum().item()) / int(d.shape[0]) if int(d.shape[0]) else float("nan")
+    precision, recall = share(_distances(s, t, o, sort, lib)), share(_distances(t, s, o, sort, lib))
+    fscore = 0.0 if precision + recall == 0 else 2 * recall * precision / (recall + precision)
+    return {"precision": precision, "recall": recall, "fscore": fscore, "transformation": T, "n_source": int(s.shape[0]),
+            "n_target": int(t.shape[0])}

@@ -51,6 +51,19 @@ class TriangleMesh:
         self.vertices = (self.vertices - c) * float(s) + c
         return self
 
+    def transform(self, transformation):
+        """Open3D's ``transform``: v <- (T [v, 1])[:3] / (T [v, 1])[3] in f64; normals, where present, go through the upper
+        3 x 3 block as Open3D's do (not renormalised)."""
+        T = np.asarray(transformation, np.float64).reshape(4, 4)
+        h = self.vertices @ T[:3, :3].T + T[:3, 3]
+        w = self.vertices @ T[3, :3] + T[3, 3]
+        self.vertices = h / w[:, None]
+        for name in ("vertex_normals", "triangle_normals"):
+            n = getattr(self, name)
+            if n.shape[0]:
+                setattr(self, name, n @ T[:3, :3].T)
+        return self
+
     def compute_triangle_normals(self):
         v = self.vertices
         t = self.triangles

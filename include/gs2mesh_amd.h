@@ -37,7 +37,8 @@ extern "C" {
                             (gs2m_tsdf_flags_device, GS2M_OPT_BIN_LANE_TILES, GS2M_OPT_PROJECT_SHARED_READ, GS2M_OPT_EXACT_TILE_CULL level 2; GS2M_OPT_BLEND_MODE 1
                             removed).  Added since without a new number: gs2m_stereo_sgm / gs2m_stereo_sgm_scratch_bytes,
                             gs2m_knn_mean_dist2 / gs2m_knn_scratch_bytes, gs2m_photo_loss_forward / _backward /
-                            _scratch_bytes, gs2m_adam_step, gs2m_densify_stats.  The Python binding checks it at load time */
+                            _scratch_bytes, gs2m_adam_step, gs2m_densify_stats, gs2m_icp_prepare / _step / _scratch_bytes,
+                            gs2m_voxel_mean.  The Python binding checks it at load time */
 
 typedef void* gs2m_stream; /* hipStream_t */
 
@@ -844,6 +845,66 @@ int gs2m_mesh_sample_emit(int64_t n_vertices, const double* vertices, int64_t n_
  */
 int gs2m_points_cull_views(int V, const float* points, int n_views, const float* proj, const uint64_t* mask_bits, int mask_width,
                            int mask_height, float norm_w, float norm_h, uint8_t* keep, gs2m_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* mesh registration: one ICP iteration, and the means of a voxel down-sample           */
+/* ------------------------------------------------------------------------------------ */
+
+/*
+ * One iteration of point-to-point ICP (Open3D's registration_icp, which the reference runs before it scores MobileBrick and
+ * TNT: evaluation/MobileBrick/eval_code/evaluate.py:82-93, evaluation/TNT/eval_code/python_toolbox/evaluation/registration.py)
+ * between source[N][3] and target[R][3], both f64: the pairs of the current transform and the moments of the kept ones.
+ *
+ * gs2m_icp_prepare, once per registration, builds the search structure of the target in `scratch`: the records, boxes and
+ * super-boxes that gs2m_nn_dist2 builds per call, of the f32 points f32(target - origin), the subtraction in f64.  It stays
+ * valid for every later gs2m_icp_step with the same target, origin and scratch, whatever their N.
+ *
+ * gs2m_icp_step, in f64 unless said otherwise, every operation rounded on its own (no FMA), parentheses = order; T the
+ * row-major 4 x 4 `transform` (its last row is not read), o the origin, s = source[i]:
+ *   p_k  = ((T[k][0] * s_x + T[k][1] * s_y) + T[k][2] * s_z) + T[k][3],  k = 0, 1, 2
+ *   j    = the nearest neighbour of f32(p - o) among f32(target - o) by the rule of gs2m_nn_dist2 (f32 distance, exact, ties
+ *          to the smallest index, a NaN distance never selected; -1 if none: R = 0, or p has a NaN coordinate)
+ *   q    = target[j],  d2 = ((p_x - q_x)^2 + (p_y - q_y)^2) + (p_z - q_z)^2
+ *   kept <=> j >= 0 and d2 < max_dist * max_dist        (strict, as Open3D's hybrid search is remembered to be; false on NaN)
+ *   p' = p - o,  q' = q - o
+ * and over the kept pairs the 18 eight-byte slots of `sums`:
+ *   [0] n, the number of kept pairs, as int64;  [1] sum d2;  [2..4] sum p';  [5..7] sum q';
+ *   [8 + 3 a + b] sum p'_a * q'_b;  [17] sum ((p'_x^2 + p'_y^2) + p'_z^2).
+ * Every f64 sum is added in one fixed order, without atomics: thread t of workgroup b adds the kept pairs among
+ * i = 1024 b + t + 256 k, k = 0 .. 3, in that order from +0; the 64 lanes of a wave by six rounds v = v + v[lane ^ m],
+ * m = 32, 16, 8, 4, 2, 1; the four waves as ((w0 + w1) + w2) + w3; the workgroups' partials t, t + 256, ... by thread t of one
+ * last workgroup, reduced the same way.  So the sums are a function of (source, T, target, o, max_dist) alone: not of the
+ * orders, not of the run.  The shift by o keeps the raw moments conditioned like the centred ones when o lies in the scene.
+ *   source, target          [N][3], [R][3] f64 device;  the same `target` that was prepared
+ *   query_order, ref_order  NULL, or [N] / [R] int32 device: as in gs2m_nn_dist2, the speed only
+ *   transform, origin       HOST, 16 and 3 f64, read before the call returns
+ *   max_dist                positive and finite, or the call is refused
+ *   scratch, scratch_bytes  device, 16-byte aligned, at least gs2m_icp_scratch_bytes(N, R); prepare needs
+ *                           gs2m_icp_scratch_bytes(0, R) of it.  Size it once for the largest N (gs2m_scratch_refused's contract)
+ *   sums                    device, 8-byte aligned, 18 * 8 bytes
+ *   out_idx, out_d2         NULL, or [N] int32 / [N] f64 device: j and d2 of every source point (d2 = +inf where j = -1)
+ * N = 0 writes zero sums; R = 0 gives n = 0 (prepare does nothing then).  Stateless apart from the scratch, asynchronous on
+ * `stream` with no host wait, no allocation; bad arguments return 1 with gs2m_last_error().
+ */
+int64_t gs2m_icp_scratch_bytes(int N, int R);
+int gs2m_icp_prepare(int R, const double* target, const double* origin, const int32_t* ref_order, void* scratch,
+                     int64_t scratch_bytes, gs2m_stream stream);
+int gs2m_icp_step(int N, const double* source, const int32_t* query_order, const double* transform, int R, const double* target,
+                  const double* origin, double max_dist, void* scratch, int64_t scratch_bytes, void* sums, int32_t* out_idx,
+                  double* out_d2, gs2m_stream stream);
+
+/*
+ * The accumulation of Open3D's PointCloud::VoxelDownSample on points already grouped by voxel: segment s is
+ * order[heads[s] .. heads[s + 1]) (the last one ends at N); means[s] = (((0 + x_0) + x_1) + ...) / count per axis in f64, the
+ * rows added in the order `order` lists them.  With `order` a stable sort by voxel key that is ascending original index, the
+ * order in which Open3D's AccumulatedPoint adds them.  An empty segment gives NaN (0 / 0).
+ *   points                  [N][3] f64 device;  order [N] int32 device;  heads [S] int32 device, ascending, heads[0] = 0
+ *   means                   [S][3] f64 device
+ * An entry of `order` outside [0, N) or a head outside [0, N] is clamped, so no access leaves the arrays.  S = 0 does nothing.
+ * Stateless, asynchronous on `stream`, no allocation, no atomics; bad arguments return 1 with gs2m_last_error().
+ */
+int gs2m_voxel_mean(int N, const double* points, const int32_t* order, int S, const int32_t* heads, double* means,
+                    gs2m_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* photometric loss of 3DGS training (L1 + D-SSIM, GS/utils/loss_utils.py, train.py:89-90) */
