@@ -76,6 +76,80 @@ GS2M_DEVICE float gs2m_add_rn(float a, float b) {
     asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// ---- one (instance, quadrant) of the compositing loop (raster_blend.h, loop forms 2 and 3), as ONE block of GCN.
+// Per lane it is exactly this (raster_blend.h states these lines as C++ for a platform without GS2M_HAS_BLEND_QUADRANT: the CPU
+// emulator of the tests runs them; GEN 0 = plain, 2 = alpha cap, 1 = alpha cap + the power > 0 test of the general path):
+//     if (q >= thr) {                                  // candidate: thr is QMIN, or 1.0 once the pixel is finished
+//         alpha = exp2(q);  [GEN: alpha = min(0.99, alpha)]  [GEN 1: alpha = q > lo ? 0 : alpha]
+//         w = T * alpha;  T = fma(-T, alpha, T);
+//         if (T < 1e-4) { T = T + w; thr = 1.0; w = 0; }          // saturated: contribution dropped, pixel finished
+//         C0 = fma(cr, w, C0);  C1 = fma(cg, w, C1);  C2 = fma(cb, w, C2);
+//     }
+// with the vector instructions the compiler emitted for those lines, in its order, under the execution mask.  What the
+// block fixes is the scalar side, which the compiler's lowering of the two `if`s cannot be talked out of:
+//   * no candidate in the wave: one taken branch over the block (as before);
+//   * candidates: s_and_saveexec and straight on -- no s_cbranch_execz behind a mask that the branch above has just
+//     proven non-empty;
+//   * the saturation fix-up sits out of line (subsection 1 of the kernel's own text section: behind its s_endpgm), so the
+//     common case is ONE NOT-TAKEN branch where the compiler laid out a taken branch around the rare block (and a second
+//     dead s_cbranch_execz inside it).
+// The execution mask is saved and restored by the block itself: it assumes nothing about the mask it is entered with.
+// Wait states (CDNA3 ISA 4.5): v_exp_f32 -> VALU use 1 (the s_nop, or the v_cmp in GEN 1); v_cmp -> v_cndmask through
+// VCC 2 (v_min + s_nop in GEN 1).  The block ends on VALU writes of C0..C2 / a SALU write of EXEC: nothing the
+// compiler's code behind it must wait for.
+#define GS2M_HAS_BLEND_QUADRANT 1
+#define GS2M_BQ_HEAD_                                                                                                   \
+    "v_cmp_ge_f32 vcc, %[q], %[thr]\n\t"                                                                                \
+    "s_cbranch_vccz .Lgs2m_bq_skip%=\n\t"                                                                               \
+    "s_and_saveexec_b64 %[sv], vcc\n\t"                                                                                 \
+    "v_exp_f32 %[al], %[q]\n\t"
+#define GS2M_BQ_TAIL_                                                                                                   \
+    "v_mul_f32 %[w], %[T], %[al]\n\t"                                                                                   \
+    "v_fma_f32 %[T], -%[T], %[al], %[T]\n\t"                                                                            \
+    "v_cmp_gt_f32 vcc, 0x38d1b717, %[T]\n\t" /* 1e-4f > T */                                                            \
+    "s_cbranch_vccnz .Lgs2m_bq_sat%=\n"                                                                                 \
+    ".Lgs2m_bq_acc%=:\n\t"                                                                                              \
+    "v_fmac_f32 %[c0], %[cr], %[w]\n\t"                                                                                 \
+    "v_fmac_f32 %[c1], %[cg], %[w]\n\t"                                                                                 \
+    "v_fmac_f32 %[c2], %[cb], %[w]\n\t"                                                                                 \
+    "s_or_b64 exec, exec, %[sv]\n"                                                                                      \
+    ".Lgs2m_bq_skip%=:\n\t"                                                                                             \
+    ".subsection 1\n"                                                                                                   \
+    ".Lgs2m_bq_sat%=:\n\t"                                                                                              \
+    "s_and_saveexec_b64 %[sv2], vcc\n\t"                                                                                \
+    "v_add_f32 %[T], %[T], %[w]\n\t"                                                                                    \
+    "v_mov_b32 %[thr], 1.0\n\t"                                                                                         \
+    "v_mov_b32 %[w], 0\n\t"                                                                                             \
+    "s_or_b64 exec, exec, %[sv2]\n\t"                                                                                   \
+    "s_branch .Lgs2m_bq_acc%=\n\t"                                                                                      \
+    ".subsection 0"
+#define GS2M_BQ_OPERANDS_                                                                                               \
+    [thr] "+v"(thr), [T] "+v"(T), [c0] "+v"(C0), [c1] "+v"(C1), [c2] "+v"(C2), [al] "=&v"(al), [w] "=&v"(w),            \
+        [sv] "=&s"(sv), [sv2] "=&s"(sv2)                                                                                \
+        : [q] "v"(q), [lo] "v"(lo), [cr] "v"(cr), [cg] "v"(cg), [cb] "v"(cb)                                            \
+        : "vcc", "scc"
+template <int GEN>
+GS2M_DEVICE void gs2m_blend_quadrant(const float q, const float lo, const float cr, const float cg, const float cb, float& thr,
+                                     float& T, float& C0, float& C1, float& C2) {
+    static_assert(GEN >= 0 && GEN <= 2, "0 plain, 1 general path, 2 alpha cap");
+    float al, w;
+    unsigned long long sv, sv2;
+    if (GEN == 0)
+        asm volatile(GS2M_BQ_HEAD_ "s_nop 0\n\t" GS2M_BQ_TAIL_ : GS2M_BQ_OPERANDS_);
+    else if (GEN == 2)
+        asm volatile(GS2M_BQ_HEAD_ "s_nop 0\n\t"
+                                   "v_min_f32 %[al], 0x3f7d70a4, %[al]\n\t" /* min(0.99f, alpha) */
+                     GS2M_BQ_TAIL_ : GS2M_BQ_OPERANDS_);
+    else
+        asm volatile(GS2M_BQ_HEAD_ "v_cmp_ngt_f32 vcc, %[q], %[lo]\n\t"
+                                   "v_min_f32 %[al], 0x3f7d70a4, %[al]\n\t"
+                                   "s_nop 0\n\t"
+                                   "v_cndmask_b32 %[al], 0, %[al], vcc\n\t" /* q > lo ? 0 : alpha */
+                     GS2M_BQ_TAIL_ : GS2M_BQ_OPERANDS_);
+}
+#undef GS2M_BQ_HEAD_
+#undef GS2M_BQ_TAIL_
+#undef GS2M_BQ_OPERANDS_
 // keep a loop-invariant float in its VGPR (stops the compiler re-materialising int->float converts in hot loops)
 #define GS2M_KEEP_F32(x) asm volatile("" : "+v"(x))
 // a wave-uniform int the compiler must treat as an opaque scalar register (stops re-association of mask tests)

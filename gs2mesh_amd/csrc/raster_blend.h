@@ -139,6 +139,31 @@ k_blend_tile256(const unsigned long long* __restrict__ keys, const unsigned* __r
 // one VALU op less, two scalar ops and a branch more), column terms only for the columns an instance reaches (+6 %),
 // 1 / 2 / 8 waves per workgroup (+-1 %), packed-f32 SLP (+18 %).
 // ---------------------------------------------------------------------------------------------
+#ifndef GS2M_HAS_BLEND_QUADRANT
+// One (instance, quadrant) of the loop forms 2 and 3, per lane: the portable statement of what hip/platform.h hand-lowers to
+// one block of GCN (there: why).  GEN 0 = plain, 2 = alpha cap (forward.cu:343), 1 = alpha cap + power > 0 skipped
+// (forward.cu:336-337).
+template <int GEN>
+GS2M_DEVICE void gs2m_blend_quadrant(const float q, const float lo, const float cr, const float cg, const float cb, float& thr,
+                                     float& T, float& C0, float& C1, float& C2) {
+    if (q >= thr) {
+        float alpha = gs2m_fast_exp2(q);
+        if (GEN != 0) alpha = fminf(0.99f, alpha);
+        if (GEN == 1) alpha = q > lo ? 0.0f : alpha;
+        float w = T * alpha;
+        T = fmaf(-T, alpha, T);     // T - alpha T with one rounding
+        if (T < 0.0001f) {          // saturated: the contribution is dropped, the pixel is finished and keeps T
+            T = gs2m_add_rn(T, w);
+            thr = 1.0f;
+            w = 0.0f;
+        }
+        C0 = fmaf(cr, w, C0);
+        C1 = fmaf(cg, w, C1);
+        C2 = fmaf(cb, w, C2);
+    }
+}
+#endif
+
 struct BlendInst {
     float4 a, b;
     float2 c;
@@ -377,33 +402,15 @@ GS2M_DEVICE void blend_tile(const int v, const int tx, const int ty, const CamUn
                 for (int k = 0; k < 4; ++k) {
                     const float dy = (k >> 1) ? p.dy1 : p.dy0;
                     const float qv = fmaf(fmaf(B.x, dy, (k & 1) ? p.n1 : p.n0), dy, (k & 1) ? p.e1 : p.e0);   // same products and sums as MODE 0
-                    const bool cand = qv >= thr[k];
-                    if (gs2m_any_active_lane(cand)) {     // v_cmp + s_cbranch_vccz
-                        GS2M_NO_IF_CONVERT();
-                        if (cand) {
-                            float alpha = gs2m_fast_exp2(qv);
-                            if (GTAG != 0) alpha = fminf(0.99f, alpha);                // alpha cap (forward.cu:343)
-                            if (GTAG == 1) alpha = qv > B.y ? 0.0f : alpha;            // power > 0: skipped (forward.cu:336-337)
-                            // Round 6: w = alpha T (the reference's own weight, forward.cu:355) and T -= alpha T IN PLACE -- the round-5
-                            // form (T' = fma(-T, alpha, T), w = T - T') kept T and T' alive together and ended every contributing
-                            // quadrant on a register copy (1 of its 8 vector instructions).  A pixel that saturates (T - alpha T <
-                            // 1e-4: its contribution is dropped, it is finished and keeps T) takes the subtraction back in the rare
-                            // path: fl(fl(T - w) + w) may differ from T in the last bit, on a transmittance < ~1e-2 that only
-                            // enters out = C + T bg; MODE 0 does the same, lane for lane.
-                            float wT = T[k] * alpha;
-                            T[k] = fmaf(-T[k], alpha, T[k]);     // T - alpha T with one rounding
-                            if (gs2m_any_active_lane(T[k] < 0.0001f)) {   // a pixel saturates once: behind a wave-uniform branch
-                                GS2M_NO_IF_CONVERT();
-                                const bool sat = T[k] < 0.0001f;
-                                thr[k] = sat ? THR_DONE : thr[k];
-                                T[k] = sat ? gs2m_add_rn(T[k], wT) : T[k];
-                                wT = sat ? 0.0f : wT;
-                            }
-                            C0[k] = fmaf(B.z, wT, C0[k]);
-                            C1[k] = fmaf(B.w, wT, C1[k]);
-                            C2[k] = fmaf(CLx, wT, C2[k]);
-                        }
-                    }
+                    // candidate test (one v_cmp against the lane's own threshold + a branch on VCC), exp2, w = alpha T (the
+                    // reference's own weight, forward.cu:355), T -= alpha T in place with one rounding, the saturation fix-up
+                    // (T - alpha T < 1e-4: the contribution is dropped, the pixel is finished and keeps T -- fl(fl(T - w) + w)
+                    // may differ from T in the last bit, on a transmittance < ~1e-2 that only enters out = C + T bg; MODE 0
+                    // does the same, lane for lane) and the three colour FMAs, under the execution mask: one block of GCN,
+                    // stated line by line in platform.h, because the compiler's lowering of the two `if`s pays a dead
+                    // s_cbranch_execz behind each tested mask and a taken branch around the rare fix-up per contributing
+                    // quadrant.  GTAG != 0: alpha cap (forward.cu:343); GTAG 1: power > 0 is skipped (forward.cu:336-337).
+                    gs2m_blend_quadrant<GTAG>(qv, B.y, B.z, B.w, CLx, thr[k], T[k], C0[k], C1[k], C2[k]);
                 }
             };
             const float4 *spa = s_a, *spb = s_b;
@@ -417,7 +424,8 @@ GS2M_DEVICE void blend_tile(const int v, const int tx, const int ty, const CamUn
                     float4 A0 = spa[j0], B0 = spb[j0], A1, B1;
                     float K0 = spc[j0].x, K1;
                     int j = j0;
-                    for (; j + 1 < j1; j += 2) {
+                    const int jl = j1 - 1;   // pairs while j < jl: the back edge is add, compare, ONE branch (`j + 1 < j1` kept a copy of j alive)
+                    for (; j < jl; j += 2) {
                         const Pre2 p0 = pre2(A0, B0);
                         GS2M_SCHED_BARRIER();
                         A1 = spa[j + 1];
