@@ -40,10 +40,8 @@ k_blend_tile256(const unsigned long long* __restrict__ keys, const unsigned* __r
     const int pxi = (int)blockIdx.x * GS2M_TILE + lx, pyi = (int)blockIdx.y * GS2M_TILE + ly;
     const bool inside = pxi < W && pyi < H;
     const float pxf = (float)pxi, pyf = (float)pyi;
-    unsigned r0 = tile_start[(size_t)v * (tiles + 1) + tile];
-    unsigned r1 = tile_start[(size_t)v * (tiles + 1) + tile + 1];
-    if (r0 > cap) r0 = cap;
-    if (r1 > cap) r1 = cap;
+    unsigned r0, r1;
+    gs2m_list_range(tile_start, v, tiles, tile, cap, r0, r1);
     const unsigned long long* kv = keys + (size_t)v * cap;
     const GeomRecs rv = gs2m_recs_at(recs, (size_t)v * P);
     bool done = !inside;
@@ -226,10 +224,8 @@ GS2M_DEVICE void blend_tile(const int v, const int tx, const int ty, const CamUn
     }
     const float qx0 = (float)(tx * GS2M_TILE), qy0 = (float)(ty * GS2M_TILE);
     const int ltile = (ty / LROWS) * gx + tx;
-    unsigned r0 = tile_start[(size_t)v * (ltiles + 1) + ltile];
-    unsigned r1 = tile_start[(size_t)v * (ltiles + 1) + ltile + 1];
-    if (r0 > cap) r0 = cap;
-    if (r1 > cap) r1 = cap;
+    unsigned r0, r1;
+    gs2m_list_range(tile_start, v, ltiles, ltile, cap, r0, r1);
     r0 = (unsigned)gs2m_uniform((int)r0);
     r1 = (unsigned)gs2m_uniform((int)r1);
     const unsigned long long* kv = keys + (size_t)v * cap;

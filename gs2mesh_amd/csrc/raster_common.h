@@ -81,6 +81,21 @@ GS2M_DEVICE unsigned gs2m_xcd_contiguous(unsigned bid, unsigned nwg) {
     return (xcd < rr ? xcd * (qq + 1u) : rr * (qq + 1u) + (xcd - rr) * qq) + idx;
 }
 
+// The key range [r0, r1) of list t of view `view` (tile_start[view][0 .. lists]), clamped to the instance arena of `cap` keys per
+// view.  After a pass that overflowed (status: N > cap) the offsets lie past the arena: this clamp is all that stands between
+// such a pass and an out-of-bounds read, so every reader of a list takes its range from here.
+GS2M_DEVICE void gs2m_list_range(const unsigned* __restrict__ tile_start, int view, int lists, int t, unsigned cap, unsigned& r0,
+                                 unsigned& r1) {
+    r0 = tile_start[(size_t)view * (lists + 1) + t];
+    r1 = tile_start[(size_t)view * (lists + 1) + t + 1];
+    if (r0 > cap) r0 = cap;
+    if (r1 > cap) r1 = cap;
+}
+// ... where tile_start is already the view's own row
+GS2M_DEVICE void gs2m_list_range(const unsigned* __restrict__ view_start, int t, unsigned cap, unsigned& r0, unsigned& r1) {
+    gs2m_list_range(view_start, 0, 0, t, cap, r0, r1);
+}
+
 // Per-view status words written by the tile scan.
 struct ViewStatus {
     unsigned num_rendered;  // instances this view produced

@@ -12,7 +12,7 @@
 // registers (raster_sort.h).  The final order is identical to the reference's: ascending depth bits, ties
 // by ascending Gaussian id (= what the stable radix sort over emission order produces).
 #pragma once
-#include "raster_math.h"
+#include "raster_bin_walk.h"
 
 // Workgroup-private tile histogram of k_count_tiles: one u32 counter per (view, tile) in LDS.  (Rounds 2-5 packed two 16-bit
 // counters per word to halve the LDS; the kernel runs one 1024-thread workgroup per CU either way -- the scatter kernel's u32
@@ -21,31 +21,6 @@
 // with the same tile) and 2 / 4 lane-interleaved copies of the histogram against the same-address serialisation of a spatially
 // ordered model's atomics: C3 count 29.7 -> 36.8 us (aggregated), 30.4 -> 29.6 (copies) -- profiles/r6_experiments.txt.)
 GS2M_DEVICE void hist_bump(unsigned* hh, int t) { atomicAdd(&hh[t], 1u); }
-
-// ---- which rects of the binning grid get what (k_count_tiles and k_scatter must agree on `tested`: it decides whether a
-// tile mask exists) ---------------------------------------------------------------------------------------------------------
-// cull = GS2M_OPT_EXACT_TILE_CULL: 0 = every tile of the (reference) rect is an instance; 1 = the rect is the bounding box of the
-// alpha >= 1/255 ellipse and every tile of a rect with corners (>= 2 x 2 tiles) is tested against the ellipse; 2 (round 6) = the
-// same, but rects of at most 4 tiles keep all their tiles -- the test only removes ~2 % of the instances of a small-splat
-// scene (C3: 3.85 M -> 3.77 M per eye) and was 60 % of the vector instructions of the counting kernel, which is VALU-issue-bound
-// (PMC round 5: 12 k vector instructions per wave, 0.8 of the SIMD's issue slots).  Rects of more than 64 tiles are walked by the
-// whole wave and test every tile.  A thin rect (one tile wide or high) is its own bounding box: never tested.
-GS2M_DEVICE bool gs2m_rect_tested(unsigned w, unsigned h, unsigned area, int cull) {
-    return cull != 0 && (area > 64u || (w >= 2u && h >= 2u && (cull == 1 || area > 4u)));
-}
-// A rect of the binning grid that is one tile wide or one tile high and has at most GS2M_THIN_MAX tiles (round 4).
-#define GS2M_THIN_MAX 4u
-GS2M_DEVICE bool gs2m_thin_rect(unsigned w, unsigned h, unsigned area) {
-    return area != 0u && area <= GS2M_THIN_MAX && (w == 1u || h == 1u);
-}
-// Rects walked by THEIR OWN LANE (no staging, no item space): the thin ones and, round 6, every rect of at most `lane_max` tiles
-// (GS2M_OPT_BIN_LANE_TILES) -- in the counting kernel only when it is not tested (the test costs ~35 vector instructions per
-// tile: a lane running it 4 times in sequence lost to the staged walk, which spreads the tiles over the lanes; measured), in
-// the scatter kernel always (it replays the mask the counting pass wrote: a bit test per tile).
-#define GS2M_LANE_TILES_MAX 16
-GS2M_DEVICE bool gs2m_lane_rect(unsigned w, unsigned h, unsigned area, unsigned lane_max) {
-    return area != 0u && (area <= lane_max || gs2m_thin_rect(w, h, area));
-}
 
 struct ProjView {
     float mx, my, ca, cb, cc, depth, cova, covc;
@@ -97,54 +72,6 @@ GS2M_DEVICE void project_view(const CamUniform& cam, float px, float py, float p
     o.depth = tvz;
     o.radius = r;
     o.ok = true;
-}
-
-// ---- wave-balanced tile expansion ------------------------------------------------------------
-// Every Gaussian touches a different number of tiles (1 ... hundreds).  Walking the rect per lane
-// (as duplicateWithKeys does, rasterizer_impl.cu:98-108) leaves most lanes idle while the wave waits for
-// its largest rect (C2: mean 8.6 tiles, mean of the per-wave maximum 38).  Instead:
-//   * the owners of small rects (<= 64 tiles) are compacted (rank k by ballot) and an exclusive wave scan
-//     of their areas flattens all their (Gaussian, tile) pairs into one item space of <= 4096 items;
-//   * a bit array marks the first item of every owner ("heads"); lane l of batch b0 takes item b0 + l and
-//     finds its owner as  k = (#heads before the batch) + popcount(heads_word & lanes <= l) - 1
-//     -- one broadcast LDS read and a popcount instead of a binary search;
-//   * rects of more than 64 tiles (rare) are walked by the whole wave, one owner at a time.
-// Each kept pair bumps the workgroup's LDS tile histogram; the kept tiles of a small rect are recorded as a
-// bit mask (assembled from ballots by the first lane of each owner's run) that the scatter kernel replays.
-struct WaveStage {
-    float mx[64], my[64], ca[64], cb[64], cc[64], thr[64], rx[64], ry[64];  // indexed by owner rank k
-    unsigned swh[64];   // first item (16 bits) | w << 16 | h << 24
-    unsigned xy0[64];   // x0 | y0 << 16
-    unsigned mlo[64], mhi[64];  // kept-tile mask of the owner's rect
-    unsigned heads[130];        // bit i: item i is the first item of an owner (+ slack for the 64-bit window)
-    unsigned pad[2];
-};
-#define GS2M_STAGE_BYTES_PER_WAVE ((int)sizeof(WaveStage))
-
-GS2M_DEVICE unsigned long long lanes_le(int lane) { return (2ull << lane) - 1ull; }
-GS2M_DEVICE unsigned long long lanes_lt(int lane) { return (1ull << lane) - 1ull; }
-
-// li -> (rx, ry) of a rect of width ow without an integer division (li < 2^16, exact after one fix-up)
-GS2M_DEVICE void rect_coords(unsigned li, unsigned ow, float inv_w, unsigned& rx, unsigned& ry) {
-    ry = (unsigned)((float)li * inv_w);
-    int r = (int)li - (int)(ry * ow);
-    if (r < 0) {
-        ry -= 1u;
-        r += (int)ow;
-    } else if (r >= (int)ow) {
-        ry += 1u;
-        r -= (int)ow;
-    }
-    rx = (unsigned)r;
-}
-
-GS2M_DEVICE unsigned wave_inclusive_scan(unsigned x) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned y = gs2m_shfl_up(x, d);
-        if (gs2m_lane() >= d) x += y;
-    }
-    return x;
 }
 
 // Projection + colour, one thread per Gaussian -- a streaming kernel (no LDS, no loop): activations, Sigma once
@@ -411,171 +338,98 @@ k_project_hc(GaussIn g, CamUniformArg hc, CamUniform* __restrict__ cams_out, Geo
     project_kernel_body<NV, DMA_SH, STREAM, true, LOOP>(g, &hc.c[0], recs, radii, exact_cull, cams_out, groups);
 }
 
-// Gaussian -> workgroup assignment of the counting sort (k_count_tiles and k_scatter must agree: the histogram row of a
-// workgroup describes exactly the Gaussians it scatters).  Step `it` of wave `wave` of the workgroup with histogram row
-// `row` starts at the returned index (64 consecutive Gaussians, one per lane); *end = one past the last index it may take;
-// returns -1 when the wave is done.
-//   contiguous (models in their stored order): the workgroup owns [row * chunk, (row + 1) * chunk) and walks it
-//     blockDim.x Gaussians at a time;
-//   interleaved (spatially ordered packed model, gs2m_raster_pack_model): blocks of 64 consecutive Gaussians are dealt
-//     round-robin to the rows.  A block is a compact screen region (its instances fall into a few tiles: the keys of a
-//     store instruction form runs), while every workgroup samples the whole model, so the work stays balanced (contiguous
-//     chunks of a Morton-ordered model differ by 2.4x in instances on C2).
-GS2M_DEVICE int bin_step_begin(int it, int wave, int nwaves, int row, int n_wg, int chunk, int P, int interleave, int* end) {
-    if (interleave) {
-        const long long first = (((long long)it * nwaves + wave) * n_wg + row) * 64ll;
-        *end = P;
-        return first < (long long)P ? (int)first : -1;
-    }
-    const int stop = gs2m_imin(P, (row + 1) * chunk);   // chunk <= 64000, rows < 2^15: no overflow
-    const long long first = (long long)row * chunk + ((long long)it * nwaves + wave) * 64ll;
-    *end = stop;
-    return first < (long long)stop ? (int)first : -1;
-}
-
 // Per-(view, Gaussian) input of the counting step: the geometry half of the GeomRec + the rect in BINNING rows.
 struct CountIn {
     float mx, my, ca, cb, cc;
     int x0, y0, x1, y1;
     bool ok;
 };
-// The tile rect of a record's binning part (16 x 16 tile units) in the binning grid (tiles of 16 x 16 * 2^rs pixels): rs = 0 / 1
-// (a shift: the signed divisions by `rows` this replaces were ~100 of the ~800 vector instructions of a C3 counting step).
-struct BinRect {
-    int x0, y0;
-    unsigned w, h, area;
+// Stage of a counting wave: the item space and, for its tested owners, what the tile test reads (indexed by owner rank k).
+struct WaveStage {
+    float mx[64], my[64], ca[64], cb[64], cc[64], thr[64], rx[64], ry[64];
+    BinItems items;
 };
-GS2M_DEVICE BinRect bin_rect_of(const float4& c, int rs) {
-    const unsigned rect0 = __float_as_uint(c.z), rect1 = __float_as_uint(c.w);
-    const int x0 = (int)(rect0 & 0xffffu), x1 = (int)(rect1 & 0xffffu);
-    const int y0 = (int)(rect0 >> 16), y1 = (int)(rect1 >> 16);
-    const bool ok = x1 > x0 && y1 > y0;
-    BinRect r;
-    r.x0 = x0;
-    r.y0 = y0 >> rs;
-    r.w = ok ? (unsigned)(x1 - x0) : 0u;
-    r.h = ok ? (unsigned)(((y1 + (1 << rs) - 1) >> rs) - r.y0) : 0u;
-    r.area = r.w * r.h;
-    return r;
-}
 
-// The counting step for the 64 Gaussians of one wave step (wave collectives: EVERY lane calls it): balanced
-// (Gaussian, tile) expansion, the workgroup's LDS tile histogram, the kept-tile masks of the tested rects.
+// The counting step for the 64 Gaussians of one wave step (wave collectives: EVERY lane calls it): the walk of raster_bin_walk.h;
+// each kept (Gaussian, tile) pair bumps the workgroup's LDS tile histogram, and the kept tiles of a tested staged rect are recorded
+// as a bit mask (assembled from ballots by the first lane of each owner's run) that the scatter kernel replays.
 template <int NV>
 GS2M_DEVICE void count_expand(const CountIn* pv, float thr, bool valid, int gi, int P, unsigned* lhist, int tiles, WaveStage* stage,
                               unsigned long long* __restrict__ tilemask, int gx, int th, int cull, int lane, unsigned lane_max) {
-    // ---- balanced (Gaussian, tile) expansion, one view at a time (wave collectives: every lane) ----
+    BinItems* const it = &stage->items;
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
+    for (int v = 0; v < NV; ++v) {   // one view at a time
         const unsigned w = (unsigned)(pv[v].x1 - pv[v].x0), h = (unsigned)(pv[v].y1 - pv[v].y0);
         const unsigned area = (valid && pv[v].ok) ? w * h : 0u;
         if (gs2m_ballot(area != 0u ? 1 : 0) == 0ull) continue;  // wave-uniform
         unsigned* hh = lhist + v * tiles;
         const unsigned xy0 = (unsigned)pv[v].x0 | ((unsigned)pv[v].y0 << 16);
-        const bool tested = gs2m_rect_tested(w, h, area, cull);
+        const BinClass rc = bin_rect_class(w, h, area, cull, lane_max, true);
         // ---- rects walked by their own lane: thin ones (round 4) and untested ones of <= lane_max tiles (round 6).  Every tile
         // is kept: no staging, no item space, no tile mask.  A 2 M-Gaussian scene of small splats is 85 % thin + 14 % 2 x 2
         // rects (C3, 16 x 32 binning tiles).
-        const bool lane_rect = !tested && gs2m_lane_rect(w, h, area, lane_max);
-        if (gs2m_ballot(lane_rect ? 1 : 0) != 0ull) {
-            // row-major walk with a running tile index (no multiplication per tile)
-            const unsigned area_l = lane_rect ? area : 0u;
-            int tile = pv[v].y0 * gx + pv[v].x0;
-            unsigned rx = 0u;
+        if (gs2m_ballot(rc.lane ? 1 : 0) != 0ull) {
+            const unsigned area_l = rc.lane ? area : 0u;
+            BinLaneCursor c = bin_lane_begin(pv[v].x0, pv[v].y0, gx);
             for (unsigned t = 0; t < area_l; ++t) {
-                hist_bump(hh, tile);
-                ++tile;
-                if (++rx == w) {
-                    rx = 0u;
-                    tile += gx - (int)w;
-                }
+                hist_bump(hh, c.tile);
+                bin_lane_next(c, w, gx);
             }
         }
         // ---- the other rects of <= 64 tiles: flattened item space ----
-        const bool small = area != 0u && area <= 64u && !lane_rect;
-        const unsigned long long smalls = gs2m_ballot(small ? 1 : 0);
-        if (smalls != 0ull) {
-            const int k = gs2m_popc64(smalls & lanes_lt(lane));
-            const unsigned incl = wave_inclusive_scan(small ? area : 0u);
-            const unsigned total = gs2m_shfl(incl, 63);
-            const unsigned start = incl - (small ? area : 0u);
-            gs2m_wave_sync();
-            stage->heads[lane] = 0u;
-            stage->heads[lane + 64] = 0u;
-            if (lane < 2) stage->heads[128 + lane] = 0u;
-            gs2m_wave_sync();
-            if (small) {
-                if (tested) {
-                    stage->mx[k] = pv[v].mx;
-                    stage->my[k] = pv[v].my;
-                    stage->ca[k] = pv[v].ca;
-                    stage->cb[k] = pv[v].cb;
-                    stage->cc[k] = pv[v].cc;
-                    stage->thr[k] = thr;
-                    cull_slopes(pv[v].ca, pv[v].cb, pv[v].cc, stage->rx[k], stage->ry[k]);
+        const unsigned long long stageds = gs2m_ballot(rc.staged ? 1 : 0);
+        if (stageds != 0ull) {
+            int k;
+            const unsigned total = bin_items_build(it, lane, rc.staged, stageds, w, h, area, xy0, rc.tested, 0ull, k,
+                                                   [&](int ko) __attribute__((always_inline)) {
+                if (rc.tested) {
+                    stage->mx[ko] = pv[v].mx;
+                    stage->my[ko] = pv[v].my;
+                    stage->ca[ko] = pv[v].ca;
+                    stage->cb[ko] = pv[v].cb;
+                    stage->cc[ko] = pv[v].cc;
+                    stage->thr[ko] = thr;
+                    cull_slopes(pv[v].ca, pv[v].cb, pv[v].cc, stage->rx[ko], stage->ry[ko]);
                 }
-                stage->swh[k] = start | (w << 16) | (h << 23) | (tested ? 0x80000000u : 0u);   // w, h <= 64: 7 bits each
-                stage->xy0[k] = xy0;
-                stage->mlo[k] = 0u;
-                stage->mhi[k] = 0u;
-                atomicOr(&stage->heads[start >> 5], 1u << (start & 31u));
-            }
-            gs2m_wave_sync();
+            });
             int kbase = 0;
             for (unsigned b0 = 0; b0 < total; b0 += 64u) {
-                const unsigned long long H =
-                    (unsigned long long)stage->heads[b0 >> 5] | ((unsigned long long)stage->heads[(b0 >> 5) + 1] << 32);
-                const int kk = kbase + gs2m_popc64(H & lanes_le(lane)) - 1;
-                kbase += gs2m_popc64(H);
-                const unsigned item = b0 + (unsigned)lane;
-                const bool act = item < total;
-                bool keep = false;
-                unsigned li = 0u;
-                if (act) {
-                    const unsigned swh = stage->swh[kk];
-                    const unsigned ow = (swh >> 16) & 0x7fu;
-                    li = item - (swh & 0xffffu);
-                    unsigned rx, ry;
-                    rect_coords(li, ow, gs2m_fast_rcp((float)ow), rx, ry);
-                    const unsigned oxy = stage->xy0[kk];
-                    const int tx = (int)(oxy & 0xffffu) + (int)rx, ty = (int)(oxy >> 16) + (int)ry;
-                    keep = true;
-                    if (swh & 0x80000000u)  // only tested rects (corners to cut)
-                        keep = tile_may_contribute(stage->mx[kk], stage->my[kk], stage->ca[kk], stage->cb[kk],
-                                                   stage->cc[kk], stage->rx[kk], stage->ry[kk], stage->thr[kk], tx, ty, th);
+                const BinItem m = bin_item(it, b0, total, lane, kbase, [&](const BinItem& m) __attribute__((always_inline)) {
+                    int tx, ty;
+                    bin_item_tile(it, m, tx, ty);
+                    bool keep = true;
+                    if (m.swh & GS2M_BIN_TESTED)  // only tested rects (corners to cut)
+                        keep = tile_may_contribute(stage->mx[m.kk], stage->my[m.kk], stage->ca[m.kk], stage->cb[m.kk],
+                                                   stage->cc[m.kk], stage->rx[m.kk], stage->ry[m.kk], stage->thr[m.kk], tx, ty, th);
                     if (keep) hist_bump(hh, ty * gx + tx);
-                }
+                    return keep;
+                });
                 // the first lane of each owner's run in this batch folds the run's keep bits into the owner's mask
-                const unsigned long long kept = gs2m_ballot(keep ? 1 : 0);
-                if (act && (lane == 0 || ((H >> lane) & 1ull))) {
-                    const unsigned long long rest = lane == 63 ? 0ull : (H >> (lane + 1));
+                const unsigned long long kept = gs2m_ballot(m.kept ? 1 : 0);
+                if (m.act && (lane == 0 || ((m.H >> lane) & 1ull))) {
+                    const unsigned long long rest = lane == 63 ? 0ull : (m.H >> (lane + 1));
                     const int len = rest ? __ffsll(rest) : 64 - lane;
                     const unsigned long long run = (kept >> lane) & (len >= 64 ? ~0ull : ((1ull << len) - 1ull));
-                    const unsigned long long bits = run << li;
-                    stage->mlo[kk] |= (unsigned)bits;
-                    stage->mhi[kk] |= (unsigned)(bits >> 32);
+                    const unsigned long long bits = run << m.li;
+                    it->mlo[m.kk] |= (unsigned)bits;
+                    it->mhi[m.kk] |= (unsigned)(bits >> 32);
                 }
             }
             gs2m_wave_sync();
-            if (small && tested)   // an untested rect keeps every tile: the scatter does not read a mask for it
-                tilemask[(size_t)v * P + gi] = (unsigned long long)stage->mlo[k] | ((unsigned long long)stage->mhi[k] << 32);
+            if (rc.staged && rc.tested)   // an untested rect keeps every tile: the scatter does not read a mask for it
+                tilemask[(size_t)v * P + gi] = (unsigned long long)it->mlo[k] | ((unsigned long long)it->mhi[k] << 32);
         }
-        // ---- rects of more than 64 tiles: the whole wave walks one owner at a time ----
-        unsigned long long bigs = gs2m_ballot(area > 64u ? 1 : 0);
+        // ---- rects of more than 64 tiles: the whole wave walks one owner at a time, its fields by shuffle ----
+        unsigned long long bigs = gs2m_ballot(rc.wave ? 1 : 0);
         while (bigs != 0ull) {
             const int o = __ffsll(bigs) - 1;
             bigs &= bigs - 1ull;
             const unsigned ow = gs2m_shfl(w, o), oa = gs2m_shfl(area, o), oxy = gs2m_shfl(xy0, o);
-            const float omx = gs2m_shfl(pv[v].mx, o), omy = gs2m_shfl(pv[v].my, o), oca = gs2m_shfl(pv[v].ca, o),
-                        ocb = gs2m_shfl(pv[v].cb, o), occ = gs2m_shfl(pv[v].cc, o), othr = gs2m_shfl(thr, o);
-            const float oinv = gs2m_fast_rcp((float)ow);
-            float orx, ory;
-            cull_slopes(oca, ocb, occ, orx, ory);
+            const BinWave ww = bin_wave_begin(ow, oxy, BinGeom{gs2m_shfl(pv[v].mx, o), gs2m_shfl(pv[v].my, o), gs2m_shfl(pv[v].ca, o),
+                                                               gs2m_shfl(pv[v].cb, o), gs2m_shfl(pv[v].cc, o), gs2m_shfl(thr, o)});
             for (unsigned li = (unsigned)lane; li < oa; li += 64u) {
-                unsigned rx, ry;
-                rect_coords(li, ow, oinv, rx, ry);
-                const int tx = (int)(oxy & 0xffffu) + (int)rx, ty = (int)(oxy >> 16) + (int)ry;
-                if (!cull || tile_may_contribute(omx, omy, oca, ocb, occ, orx, ory, othr, tx, ty, th)) hist_bump(hh, ty * gx + tx);
+                int tile;
+                if (bin_wave_tile(ww, li, cull, gx, th, tile)) hist_bump(hh, tile);
             }
         }
     }
@@ -592,23 +446,15 @@ k_count_tiles(GeomRecs recs, int P, const CamUniform* __restrict__ cams, int chu
     GS2M_DYN_LDS(unsigned, lds);
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63, wave = gs2m_uniform(tid >> 6);
-    const int gx = cams[0].gx, th = cams[0].th, rs = GS2M_CAM_ROWS(cams[0]) >> 1;   // rows = 1 / 2 -> shift 0 / 1
-    const int tiles = gx * GS2M_CAM_GYS(cams[0]);
-    const unsigned lane_max = (unsigned)gs2m_uniform(lane_tiles);
-    const int cull = gs2m_uniform(exact_cull);
-    // blockIdx.y = group of NV views of the launch (GS2M_OPT_PAIR_BATCH): its own records, masks and histogram rows
-    cams += NV * blockIdx.y;
-    recs = gs2m_recs_at(recs, (size_t)NV * blockIdx.y * P);
-    tilemask += (size_t)NV * blockIdx.y * P;
-    hist += (size_t)NV * blockIdx.y * n_wg * tiles;
+    const BinGrid bg = bin_prologue<NV>(cams, recs, P, n_wg, tilemask, hist, exact_cull, lane_tiles);   // moves the four pointers to this group of views
+    const int gx = bg.gx, th = bg.th, rs = bg.rs, tiles = bg.tiles, cull = bg.cull;
     // workgroup-private tile histogram: one u32 counter per (view, tile)
     const int nthreads = (int)blockDim.x;
     unsigned* lhist = lds;
-    WaveStage* stage = reinterpret_cast<WaveStage*>(lds + ((NV * tiles + 3) & ~3)) + wave;
+    WaveStage* stage = bin_stage<NV, WaveStage>(lds, tiles, wave);
     for (int i = tid; i < NV * tiles; i += nthreads) lhist[i] = 0u;
     __syncthreads();
-    // histogram row of this workgroup: the workgroups of an XCD own consecutive rows (see k_scatter)
-    const int row = (int)gs2m_xcd_contiguous(blockIdx.x, (unsigned)n_wg);
+    const int row = bin_row(n_wg);
     // Two-stage prefetch (round 6).  The 16-B binning part of the records (depth + rect) is loaded TWO wave steps ahead; the 32-B
     // geometry part one step ahead and ONLY for the lanes whose rect is tested -- nothing else of the counting step reads it
     // (round 5 streamed 48 B per (view, Gaussian) through this kernel, 32 of them unused for the thin rects that make up
@@ -672,7 +518,7 @@ k_count_tiles(GeomRecs recs, int P, const CamUniform* __restrict__ cams, int chu
             }
         }
         const float thr = any_tested ? cull_threshold(op) : 0.0f;   // one logarithm per tested Gaussian (it was one per view and record)
-        count_expand<NV>(pv, thr, valid, gi, P, lhist, tiles, stage, tilemask, gx, th, cull, lane, lane_max);
+        count_expand<NV>(pv, thr, valid, gi, P, lhist, tiles, stage, tilemask, gx, th, cull, lane, bg.lane_max);
         first = first_n;
         end = end_n;
         first_n = first_nn;
@@ -690,19 +536,17 @@ k_count_tiles(GeomRecs recs, int P, const CamUniform* __restrict__ cams, int chu
         for (int t = tid; t < tiles; t += nthreads) hist[((size_t)v * n_wg + row) * tiles + t] = lhist[v * tiles + t];
 }
 
+// Stage of a scatter wave: the item space and the two halves of every owner's sort key (indexed by owner rank k).
 struct ScatterStage {
-    unsigned swh[64], xy0[64], dbits[64], gid[64], mlo[64], mhi[64];  // indexed by owner rank k
-    unsigned heads[130];
-    unsigned pad[2];
+    unsigned dbits[64], gid[64];
+    BinItems items;
 };
-#define GS2M_SCATTER_STAGE_BYTES_PER_WAVE ((int)sizeof(ScatterStage))
 
 // Instance scatter: same Gaussian -> workgroup assignment as k_count_tiles; cursors start at
 // tile_start[v][t] + (exclusive prefix over workgroups, left in `hist` by k_hist_colscan).
 // Key = depth_bits << 32 | gaussian_id (unique => order after the per-tile sort is deterministic
-// although LDS-atomic arrival order is not).  Rects of <= lane_max tiles are emitted by their own lane, the other rects of
-// <= 64 tiles through the balanced walk of k_count_tiles; tested rects replay the tile mask written there, rects of more than
-// 64 tiles repeat the same per-tile test.
+// although LDS-atomic arrival order is not).  The walk is the counting pass's (raster_bin_walk.h); tested rects replay the tile
+// mask written there, rects of more than 64 tiles repeat the same per-tile test.
 template <int NV>
 GS2M_KERNEL void __launch_bounds__(1024)
 k_scatter(GeomRecs recs, int P, const CamUniform* __restrict__ cams, int chunk, int n_wg,
@@ -712,28 +556,19 @@ k_scatter(GeomRecs recs, int P, const CamUniform* __restrict__ cams, int chunk, 
     GS2M_DYN_LDS(unsigned, cursor);
     const int tid = (int)threadIdx.x;
     const int nthreads = (int)blockDim.x;
-    const int gx = cams[0].gx, th = cams[0].th, rs = GS2M_CAM_ROWS(cams[0]) >> 1;
-    const int tiles = gx * GS2M_CAM_GYS(cams[0]);
-    const unsigned lane_max = (unsigned)gs2m_uniform(lane_tiles);
-    const int cull = gs2m_uniform(exact_cull);
-    // blockIdx.y = group of NV views of the launch (GS2M_OPT_PAIR_BATCH)
-    cams += NV * blockIdx.y;
-    recs = gs2m_recs_at(recs, (size_t)NV * blockIdx.y * P);
-    tilemask += (size_t)NV * blockIdx.y * P;
-    hist += (size_t)NV * blockIdx.y * n_wg * tiles;
+    const int lane = tid & 63, wave = gs2m_uniform(tid >> 6);
+    const BinGrid bg = bin_prologue<NV>(cams, recs, P, n_wg, tilemask, hist, exact_cull, lane_tiles);   // moves the four pointers to this group of views
+    const int gx = bg.gx, th = bg.th, rs = bg.rs, tiles = bg.tiles, cull = bg.cull;
     tile_start += (size_t)NV * blockIdx.y * (tiles + 1);
     keys += (size_t)NV * blockIdx.y * cap;
-    // Chunk (= histogram row = position of this workgroup's segment inside every tile's key range).  The workgroups of
-    // one XCD own consecutive rows, so the segments an XCD writes into a tile are adjacent: its 8-B key stores fill
-    // whole lines in ITS L2 instead of leaving 1/8-written lines in eight L2s (4x write amplification, PMC WRITE_SIZE).
-    const int row = (int)gs2m_xcd_contiguous(blockIdx.x, (unsigned)n_wg);
+    const int row = bin_row(n_wg);
     for (int v = 0; v < NV; ++v)
         for (int t = tid; t < tiles; t += nthreads)
             cursor[v * tiles + t] = tile_start[(size_t)v * (tiles + 1) + t] + hist[((size_t)v * n_wg + row) * tiles + t];
     __syncthreads();
-    const int lane = tid & 63, wave = gs2m_uniform(tid >> 6);
     const int nw = nthreads >> 6;
-    ScatterStage* stage = reinterpret_cast<ScatterStage*>(cursor + ((NV * tiles + 3) & ~3)) + wave;
+    ScatterStage* const stage = bin_stage<NV, ScatterStage>(cursor, tiles, wave);
+    BinItems* const it = &stage->items;
     // one view after the other: the key lines this XCD is filling at any time belong to ONE view's array (half the L2
     // working set of a walk that alternates between the views)
 #pragma unroll
@@ -757,7 +592,7 @@ k_scatter(GeomRecs recs, int P, const CamUniform* __restrict__ cams, int chunk, 
             }
         };
         fetch(first, end);
-        for (int it = 0;; ++it) {
+        for (int step = 0;; ++step) {
             if (first < 0) break;   // wave-uniform
             const int gi = first + lane;
             const bool valid = gi < end;
@@ -766,28 +601,26 @@ k_scatter(GeomRecs recs, int P, const CamUniform* __restrict__ cams, int chunk, 
             unsigned long long msk_pre = n_msk;
             {
                 int end_next = 0;
-                const int first_next = bin_step_begin(it + 1, wave, nw, row, n_wg, chunk, P, interleave, &end_next);
+                const int first_next = bin_step_begin(step + 1, wave, nw, row, n_wg, chunk, P, interleave, &end_next);
                 fetch(first_next, end_next);
                 first = first_next;      // rotated here: the wave-uniform `continue` below skips nothing of the pipeline
                 end = end_next;
             }
-            const BinRect rc = bin_rect_of(w2, rs);
+            const BinRect q = bin_rect_of(w2, rs);
             const unsigned dbits = __float_as_uint(w2.y);
-            const int x0 = rc.x0, y0 = rc.y0;
-            const unsigned rect0 = (unsigned)x0 | ((unsigned)y0 << 16);
-            const unsigned w = rc.w, h = rc.h, area = valid ? rc.area : 0u;
+            const unsigned xy0 = (unsigned)q.x0 | ((unsigned)q.y0 << 16);
+            const unsigned w = q.w, h = q.h, area = valid ? q.area : 0u;
             if (gs2m_ballot(area != 0u ? 1 : 0) == 0ull) continue;  // wave-uniform
-            if (!gs2m_rect_tested(w, h, area, cull)) msk_pre = ~0ull;   // the word loaded for an untested rect is not a mask
+            const BinClass rc = bin_rect_class(w, h, area, cull, bg.lane_max, false);
+            if (!rc.tested) msk_pre = ~0ull;   // the word loaded for an untested rect is not a mask
             unsigned* cur = cursor + v * tiles;
             unsigned long long* kv = keys + (size_t)v * cap;
-            // rects of <= lane_max tiles (and the thin ones): the lane emits its own keys, replaying its mask (all ones when the
-            // rect was not tested), row-major bits
-            const bool lane_rect = gs2m_lane_rect(w, h, area, lane_max);
-            if (gs2m_ballot(lane_rect ? 1 : 0) != 0ull) {
-                const unsigned area_l = lane_rect ? area : 0u;
+            // rects walked by their own lane: the lane emits its own keys, replaying its mask (all ones when the rect was not
+            // tested), row-major bits
+            if (gs2m_ballot(rc.lane ? 1 : 0) != 0ull) {
+                const unsigned area_l = rc.lane ? area : 0u;
                 const unsigned long long key = ((unsigned long long)dbits << 32) | kid;
-                int tile = y0 * gx + x0;
-                unsigned rx = 0u;
+                BinLaneCursor c = bin_lane_begin(q.x0, q.y0, gx);
                 // four tiles per round: the (returning) LDS atomics of a round are issued back to back and waited for ONCE, then
                 // the key stores (rounds 4-5 ran one atomic -> wait -> store chain per tile: four LDS round trips in sequence
                 // for a 2 x 2 rect)
@@ -797,65 +630,38 @@ k_scatter(GeomRecs recs, int P, const CamUniform* __restrict__ cams, int chunk, 
                     for (int u = 0; u < 4; ++u) {
                         const unsigned t = t0 + (unsigned)u;
                         pos[u] = cap;
-                        if (t < area_l && ((msk_pre >> t) & 1ull) != 0ull) pos[u] = atomicAdd(&cur[tile], 1u);
-                        ++tile;
-                        if (++rx == w) {
-                            rx = 0u;
-                            tile += gx - (int)w;
-                        }
+                        if (t < area_l && ((msk_pre >> t) & 1ull) != 0ull) pos[u] = atomicAdd(&cur[c.tile], 1u);
+                        bin_lane_next(c, w, gx);
                     }
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
                         if (pos[u] < cap) kv[pos[u]] = key;
                 }
             }
-            const bool small = area != 0u && area <= 64u && !lane_rect;
-            const unsigned long long smalls = gs2m_ballot(small ? 1 : 0);
-            if (smalls != 0ull) {
-                const unsigned long long msk = small ? msk_pre : 0ull;
-                const int k = gs2m_popc64(smalls & lanes_lt(lane));
-                const unsigned incl = wave_inclusive_scan(small ? area : 0u);
-                const unsigned total = gs2m_shfl(incl, 63);
-                const unsigned start = incl - (small ? area : 0u);
-                gs2m_wave_sync();
-                stage->heads[lane] = 0u;
-                stage->heads[lane + 64] = 0u;
-                if (lane < 2) stage->heads[128 + lane] = 0u;
-                gs2m_wave_sync();
-                if (small) {
-                    stage->swh[k] = start | (w << 16) | (h << 24);
-                    stage->xy0[k] = rect0;
-                    stage->dbits[k] = dbits;
-                    stage->gid[k] = kid;
-                    stage->mlo[k] = (unsigned)msk;
-                    stage->mhi[k] = (unsigned)(msk >> 32);
-                    atomicOr(&stage->heads[start >> 5], 1u << (start & 31u));
-                }
-                gs2m_wave_sync();
+            const unsigned long long stageds = gs2m_ballot(rc.staged ? 1 : 0);
+            if (stageds != 0ull) {
+                int k;
+                const unsigned total = bin_items_build(it, lane, rc.staged, stageds, w, h, area, xy0, rc.tested, msk_pre, k,
+                                                       [&](int ko) __attribute__((always_inline)) {
+                    stage->dbits[ko] = dbits;
+                    stage->gid[ko] = kid;
+                });
                 int kbase = 0;
                 // one 64-item batch: owner lookup, mask bit, cursor bump -> (position, key) of this lane's item (position `cap`: none)
                 auto emit = [&](unsigned b0, unsigned& pos, unsigned long long& key) __attribute__((always_inline)) {
-                    const unsigned long long H =
-                        (unsigned long long)stage->heads[b0 >> 5] | ((unsigned long long)stage->heads[(b0 >> 5) + 1] << 32);
-                    const int kk = kbase + gs2m_popc64(H & lanes_le(lane)) - 1;
-                    kbase += gs2m_popc64(H);
-                    const unsigned item = b0 + (unsigned)lane;
                     pos = cap;
                     key = 0ull;
-                    if (item < total) {
-                        const unsigned swh = stage->swh[kk];
-                        const unsigned li = item - (swh & 0xffffu);
-                        const unsigned long long om = (unsigned long long)stage->mlo[kk] | ((unsigned long long)stage->mhi[kk] << 32);
-                        if ((om >> li) & 1ull) {
-                            const unsigned ow = (swh >> 16) & 0xffu;
-                            unsigned rx, ry;
-                            rect_coords(li, ow, gs2m_fast_rcp((float)ow), rx, ry);
-                            const unsigned oxy = stage->xy0[kk];
-                            const int tx = (int)(oxy & 0xffffu) + (int)rx, ty = (int)(oxy >> 16) + (int)ry;
-                            key = ((unsigned long long)stage->dbits[kk] << 32) | stage->gid[kk];
+                    bin_item(it, b0, total, lane, kbase, [&](const BinItem& m) __attribute__((always_inline)) {
+                        const unsigned long long om = (unsigned long long)it->mlo[m.kk] | ((unsigned long long)it->mhi[m.kk] << 32);
+                        const bool keep = ((om >> m.li) & 1ull) != 0ull;
+                        if (keep) {
+                            int tx, ty;
+                            bin_item_tile(it, m, tx, ty);
+                            key = ((unsigned long long)stage->dbits[m.kk] << 32) | stage->gid[m.kk];
                             pos = atomicAdd(&cur[ty * gx + tx], 1u);
                         }
-                    }
+                        return keep;
+                    });
                 };
                 // two batches per round, the key store of a batch BEHIND the next batch's cursor bump: the returning LDS atomic of
                 // batch A is waited for together with the stage reads of batch B (LDS operations return in order), not on its own
@@ -871,34 +677,25 @@ k_scatter(GeomRecs recs, int P, const CamUniform* __restrict__ cams, int chunk, 
                 }
                 if (pos_b < cap) kv[pos_b] = key_b;
             }
-            // rects of more than 64 tiles (rare): the whole wave walks one owner at a time, repeating the test
-            unsigned long long bigs = gs2m_ballot(area > 64u ? 1 : 0);
+            // rects of more than 64 tiles (rare): the whole wave walks one owner at a time, its geometry from the record
+            unsigned long long bigs = gs2m_ballot(rc.wave ? 1 : 0);
             while (bigs != 0ull) {
                 const int o = __ffsll(bigs) - 1;
                 bigs &= bigs - 1ull;
-                const unsigned ow = gs2m_shfl(w, o), oa = gs2m_shfl(area, o), oxy = gs2m_shfl(rect0, o);
+                const unsigned ow = gs2m_shfl(w, o), oa = gs2m_shfl(area, o), oxy = gs2m_shfl(xy0, o);
                 const unsigned long long key = ((unsigned long long)gs2m_shfl(dbits, o) << 32) | gs2m_shfl(kid, o);
-                float mx = 0.f, my = 0.f, ca = 0.f, cb = 0.f, cc = 0.f, thr = 0.f;
+                BinGeom og{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 if (cull) {
                     const float4* r4 = recs.ab + 2 * ((size_t)v * P + gs2m_shfl(gi, o));
                     const float4 w0 = r4[0];
                     const float4 w1 = r4[1];
-                    mx = w0.x;
-                    my = w0.y;
-                    ca = w0.z;
-                    cb = w0.w;
-                    cc = w1.x;
-                    thr = cull_threshold(w1.y);
+                    og = BinGeom{w0.x, w0.y, w0.z, w0.w, w1.x, cull_threshold(w1.y)};
                 }
-                float srx, sry;
-                cull_slopes(ca, cb, cc, srx, sry);
-                const float oinv = gs2m_fast_rcp((float)ow);
+                const BinWave ww = bin_wave_begin(ow, oxy, og);
                 for (unsigned li = (unsigned)lane; li < oa; li += 64u) {
-                    unsigned rx, ry;
-                    rect_coords(li, ow, oinv, rx, ry);
-                    const int tx = (int)(oxy & 0xffffu) + (int)rx, ty = (int)(oxy >> 16) + (int)ry;
-                    if (!cull || tile_may_contribute(mx, my, ca, cb, cc, srx, sry, thr, tx, ty, th)) {
-                        const unsigned pos = atomicAdd(&cur[ty * gx + tx], 1u);
+                    int tile;
+                    if (bin_wave_tile(ww, li, cull, gx, th, tile)) {
+                        const unsigned pos = atomicAdd(&cur[tile], 1u);
                         if (pos < cap) kv[pos] = key;
                     }
                 }

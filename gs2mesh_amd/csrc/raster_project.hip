@@ -9,12 +9,28 @@ int gs2m_count_threads(int chunk, int max_threads) {
     const int t = chunk < cap ? (chunk + 63) / 64 * 64 : cap;
     return t < 64 ? 64 : t;
 }
-size_t gs2m_count_lds_bytes(int nv, int tiles, int threads) {
-    return (size_t)((nv * tiles + 3) & ~3) * sizeof(unsigned) + (size_t)(threads / 64) * GS2M_STAGE_BYTES_PER_WAVE;
+// dynamic LDS of a counting / scatter workgroup: one u32 per (view, tile) + one stage per wave (bin_prologue places them)
+static size_t bin_lds_bytes(int nv, int tiles, int threads, size_t stage_bytes) {
+    return (size_t)((nv * tiles + 3) & ~3) * sizeof(unsigned) + (size_t)(threads / 64) * stage_bytes;
 }
+size_t gs2m_count_lds_bytes(int nv, int tiles, int threads) { return bin_lds_bytes(nv, tiles, threads, sizeof(WaveStage)); }
+size_t gs2m_scatter_lds_bytes(int nv, int tiles, int threads) { return bin_lds_bytes(nv, tiles, threads, sizeof(ScatterStage)); }
 
-size_t gs2m_scatter_lds_bytes(int nv, int tiles, int threads) {
-    return (size_t)((nv * tiles + 3) & ~3) * sizeof(unsigned) + (size_t)(threads / 64) * GS2M_SCATTER_STAGE_BYTES_PER_WAVE;
+// Launch of k_count_tiles / k_scatter: k1 / k2 = the kernel for one view / a stereo pair per group, grid = n_wg workgroups x
+// `pairs` groups; more than 64 KiB of dynamic LDS has to be asked for first.
+template <class K, class... Args>
+static int bin_launch(const char* name, K k1, K k2, int nv, int pairs, int n_wg, int threads, size_t lds_bytes, hipStream_t st,
+                      Args... args) {
+    const K k = nv == 2 ? k2 : k1;
+    if (lds_bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) {
+            gs2m_set_error("hipFuncSetAttribute(%s, %zu B LDS): %s", name, lds_bytes, hipGetErrorString(e));
+            return 1;
+        }
+    }
+    GS2M_LAUNCH(k, dim3(n_wg, pairs), dim3(threads), lds_bytes, st, args...);
+    return 0;
 }
 
 void gs2m_launch_project(int nv, int pairs, hipStream_t st, const GaussIn& g, CamUniform* cams, GeomRecs recs, int* radii,
@@ -60,46 +76,16 @@ void gs2m_launch_project(int nv, int pairs, hipStream_t st, const GaussIn& g, Ca
 int gs2m_launch_count_tiles(int nv, int pairs, int n_wg, int threads, size_t lds_bytes, hipStream_t st, GeomRecs recs, int P,
                             const CamUniform* cams, int chunk, unsigned* hist, unsigned long long* tilemask,
                             int exact_cull, int interleave, int lane_tiles) {
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = nv == 2 ? hipFuncSetAttribute((const void*)k_count_tiles<2>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)
-                               : hipFuncSetAttribute((const void*)k_count_tiles<1>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) {
-            gs2m_set_error("hipFuncSetAttribute(k_count_tiles, %zu B LDS): %s", lds_bytes, hipGetErrorString(e));
-            return 1;
-        }
-    }
-    if (nv == 2)
-        GS2M_LAUNCH((k_count_tiles<2>), dim3(n_wg, pairs), dim3(threads), lds_bytes, st, recs, P, cams, chunk, n_wg, hist, tilemask,
-                    exact_cull, interleave, lane_tiles);
-    else
-        GS2M_LAUNCH((k_count_tiles<1>), dim3(n_wg, pairs), dim3(threads), lds_bytes, st, recs, P, cams, chunk, n_wg, hist, tilemask,
-                    exact_cull, interleave, lane_tiles);
-    return 0;
+    return bin_launch("k_count_tiles", k_count_tiles<1>, k_count_tiles<2>, nv, pairs, n_wg, threads, lds_bytes, st, recs, P, cams,
+                      chunk, n_wg, hist, tilemask, exact_cull, interleave, lane_tiles);
 }
 
 int gs2m_launch_scatter(int nv, int pairs, int n_wg, int threads, size_t lds_bytes, hipStream_t st, GeomRecs recs, int P,
                         const CamUniform* cams, int chunk, const unsigned* hist, const unsigned* tile_start,
                         const unsigned long long* tilemask, unsigned long long* keys, unsigned cap, int exact_cull,
                         const int* ids, int interleave, int lane_tiles) {
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = nv == 2 ? hipFuncSetAttribute((const void*)k_scatter<2>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)
-                               : hipFuncSetAttribute((const void*)k_scatter<1>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) {
-            gs2m_set_error("hipFuncSetAttribute(k_scatter, %zu B LDS): %s", lds_bytes, hipGetErrorString(e));
-            return 1;
-        }
-    }
-    if (nv == 2)
-        GS2M_LAUNCH((k_scatter<2>), dim3(n_wg, pairs), dim3(threads), lds_bytes, st, recs, P, cams, chunk, n_wg, hist,
-                    tile_start, tilemask, keys, cap, exact_cull, ids, interleave, lane_tiles);
-    else
-        GS2M_LAUNCH((k_scatter<1>), dim3(n_wg, pairs), dim3(threads), lds_bytes, st, recs, P, cams, chunk, n_wg, hist,
-                    tile_start, tilemask, keys, cap, exact_cull, ids, interleave, lane_tiles);
-    return 0;
+    return bin_launch("k_scatter", k_scatter<1>, k_scatter<2>, nv, pairs, n_wg, threads, lds_bytes, st, recs, P, cams, chunk, n_wg,
+                      hist, tile_start, tilemask, keys, cap, exact_cull, ids, interleave, lane_tiles);
 }
 
 void gs2m_launch_pack_sh(hipStream_t st, int P, const float* shs, const float* shs_rest, float* packed, const int* order) {

@@ -479,6 +479,49 @@ GS2M_DEVICE bool sort_wave_bucket(unsigned long long* __restrict__ kv, const int
     return true;
 }
 
+// Rank-merge passes over a list of n unique keys that stands in `src` (= kv or tv) as sorted runs of w0 keys: a key's place in
+// the merge of two sibling runs is its index in its own run + the lower bound in the sibling.  The passes ping-pong between kv
+// and tv; the sorted list is left in kv.  One workgroup of 256 threads (all call it): a pass reads what other threads of the
+// workgroup wrote to global memory -- same CU, same L1 -> visible after the workgroup barrier.
+GS2M_DEVICE void sort_rank_merge(unsigned long long* kv, unsigned long long* tv, unsigned long long* src, const int n, const int w0,
+                                 const int tid) {
+    unsigned long long* dst = src == kv ? tv : kv;
+    for (int w = w0; w < n; w <<= 1) {
+        for (int i = tid; i < n; i += 256) {
+            const int blk = i / (2 * w);
+            const int a0 = blk * 2 * w;
+            const int a1 = a0 + w < n ? a0 + w : n;            // A = [a0,a1)
+            const int b1 = a0 + 2 * w < n ? a0 + 2 * w : n;    // B = [a1,b1)
+            const unsigned long long key = src[i];
+            int lo, hi, base;
+            if (i < a1) {  // element of A: count of B elements smaller than key
+                lo = a1;
+                hi = b1;
+                base = i - a0;
+            } else {
+                lo = a0;
+                hi = a1;
+                base = i - a1;
+            }
+            const int lo0 = lo;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (src[mid] < key) lo = mid + 1;
+                else hi = mid;
+            }
+            dst[a0 + base + (lo - lo0)] = key;
+        }
+        __syncthreads();
+        unsigned long long* x = src;
+        src = dst;
+        dst = x;
+    }
+    if (src != kv) {
+        for (int i = tid; i < n; i += 256) kv[i] = src[i];
+    }
+    __syncthreads();
+}
+
 // LDS-free stand-in for the three size-class kernels, launched INSTEAD of them when the previous call on the handle found
 // every class empty (the usual case at 16 x 32 tiles of a 300 k-Gaussian model: no list above 512 instances).  The class
 // kernels carry 40-80 KiB of static LDS per workgroup; under the pipelined load (a compositing grid of another stream holds
@@ -502,10 +545,8 @@ GS2M_DEVICE void sort_class_lists_rank(unsigned long long* __restrict__ keys, un
         const unsigned count = list[0];
         for (unsigned li = first; li < count; li += stride) {
             const int t = (int)list[1 + li];
-            unsigned b = tile_start[(size_t)v * (tiles + 1) + t];
-            unsigned e = tile_start[(size_t)v * (tiles + 1) + t + 1];
-            if (b > cap) b = cap;
-            if (e > cap) e = cap;
+            unsigned b, e;
+            gs2m_list_range(tile_start, v, tiles, t, cap, b, e);
             const int n = (int)(e - b);
             unsigned long long* kv = keys + (size_t)v * cap + b;
             unsigned long long* tv = tmp + (size_t)v * cap + b;
@@ -520,42 +561,7 @@ GS2M_DEVICE void sort_class_lists_rank(unsigned long long* __restrict__ keys, un
                 }
             }
             __syncthreads();
-            unsigned long long* src = tv;
-            unsigned long long* dst = kv;
-            for (int w = 256; w < n; w <<= 1) {
-                for (int i = tid; i < n; i += 256) {
-                    const int blk = i / (2 * w);
-                    const int a0 = blk * 2 * w;
-                    const int a1 = a0 + w < n ? a0 + w : n;            // A = [a0,a1)
-                    const int b1 = a0 + 2 * w < n ? a0 + 2 * w : n;    // B = [a1,b1)
-                    const unsigned long long key = src[i];
-                    int lo, hi, base;
-                    if (i < a1) {  // element of A: count of B elements smaller than key
-                        lo = a1;
-                        hi = b1;
-                        base = i - a0;
-                    } else {
-                        lo = a0;
-                        hi = a1;
-                        base = i - a1;
-                    }
-                    const int lo0 = lo;
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        if (src[mid] < key) lo = mid + 1;
-                        else hi = mid;
-                    }
-                    dst[a0 + base + (lo - lo0)] = key;
-                }
-                __syncthreads();
-                unsigned long long* x = src;
-                src = dst;
-                dst = x;
-            }
-            if (src != kv) {
-                for (int i = tid; i < n; i += 256) kv[i] = src[i];
-            }
-            __syncthreads();
+            sort_rank_merge(kv, tv, tv, n, 256, tid);
         }
     }
 }
@@ -575,10 +581,8 @@ k_sort_tiles_small(unsigned long long* __restrict__ keys, const unsigned* __rest
     unsigned* s_fine = s_fine_all[wave];
     const int t = gs2m_uniform((int)blockIdx.x * WPB + wave), v = (int)blockIdx.y;
     if (t < tiles) {
-        unsigned b = tile_start[(size_t)v * (tiles + 1) + t];
-        unsigned e = tile_start[(size_t)v * (tiles + 1) + t + 1];
-        if (b > cap) b = cap;
-        if (e > cap) e = cap;
+        unsigned b, e;
+        gs2m_list_range(tile_start, v, tiles, t, cap, b, e);
         const int n = (int)(e - b);
         unsigned long long* kv = keys + (size_t)v * cap + b;
         if (n <= 1 || n > GS2M_SORT_WAVE) {
@@ -837,10 +841,8 @@ GS2M_DEVICE void sort_tiles_bucket_body(unsigned long long* __restrict__ keys, c
     const unsigned count = list[0];
     for (unsigned li = blockIdx.x; li < count; li += gridDim.x) {
         const int t = (int)list[1 + li];
-        unsigned b0 = tile_start[(size_t)v * (tiles + 1) + t];
-        unsigned e0 = tile_start[(size_t)v * (tiles + 1) + t + 1];
-        if (b0 > cap) b0 = cap;
-        if (e0 > cap) e0 = cap;
+        unsigned b0, e0;
+        gs2m_list_range(tile_start, v, tiles, t, cap, b0, e0);
         const int n = (int)(e0 - b0);
         if (n > 1) {
             if (n <= CAP) sort_list_bucket<CAP, THREADS>(keys + (size_t)v * cap + b0, n, s_key, s_cnt, s_red, tid);
@@ -875,10 +877,8 @@ k_sort_tiles(unsigned long long* __restrict__ keys, unsigned long long* __restri
     const unsigned count = list[0];
     for (unsigned li = blockIdx.x; li < count; li += gridDim.x) {
         const int t = (int)list[1 + li];
-        unsigned b = tile_start[(size_t)v * (tiles + 1) + t];
-        unsigned e = tile_start[(size_t)v * (tiles + 1) + t + 1];
-        if (b > cap) b = cap;
-        if (e > cap) e = cap;
+        unsigned b, e;
+        gs2m_list_range(tile_start, v, tiles, t, cap, b, e);
         const int n = (int)(e - b);
         unsigned long long* kv = keys + (size_t)v * cap + b;
         unsigned long long* tv = tmp + (size_t)v * cap + b;
@@ -891,42 +891,7 @@ k_sort_tiles(unsigned long long* __restrict__ keys, unsigned long long* __restri
             else sort_block_regs<16>(kv + r0, rn, s, tid);
             __syncthreads();
         }
-        unsigned long long* src = kv;
-        unsigned long long* dst = tv;
-        for (int w = GS2M_SORT_LDS; w < n; w <<= 1) {
-            for (int i = tid; i < n; i += 256) {
-                const int blk = i / (2 * w);
-                const int a0 = blk * 2 * w;
-                const int a1 = a0 + w < n ? a0 + w : n;            // A = [a0,a1)
-                const int b1 = a0 + 2 * w < n ? a0 + 2 * w : n;    // B = [a1,b1)
-                const unsigned long long key = src[i];
-                int lo, hi, base;
-                if (i < a1) {  // element of A: count of B elements smaller than key
-                    lo = a1;
-                    hi = b1;
-                    base = i - a0;
-                } else {
-                    lo = a0;
-                    hi = a1;
-                    base = i - a1;
-                }
-                const int lo0 = lo;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (src[mid] < key) lo = mid + 1;
-                    else hi = mid;
-                }
-                dst[a0 + base + (lo - lo0)] = key;
-            }
-            __syncthreads();
-            unsigned long long* x = src;
-            src = dst;
-            dst = x;
-        }
-        if (src != kv) {
-            for (int i = tid; i < n; i += 256) kv[i] = src[i];
-        }
-        __syncthreads();
+        sort_rank_merge(kv, tv, kv, n, GS2M_SORT_LDS, tid);
     }
 }
 

@@ -40,9 +40,8 @@ GS2M_DEVICE TileWalk walk_tile(const int tile, const unsigned* __restrict__ tile
     t.lane = (int)(threadIdx.x & 63u);
     t.ty = tile / gx;
     t.tx = tile - t.ty * gx;
-    unsigned r0 = tile_start[tile], r1 = tile_start[tile + 1];
-    if (r0 > cap) r0 = cap;
-    if (r1 > cap) r1 = cap;
+    unsigned r0, r1;
+    gs2m_list_range(tile_start, tile, cap, r0, r1);   // tile_start is this view's own row
     t.r0 = (unsigned)gs2m_uniform((int)r0);
     t.r1 = (unsigned)gs2m_uniform((int)r1);
 #pragma unroll

@@ -376,7 +376,7 @@ int64_t oracle_bin(int P, int W, int H, const int* radii, const float* means2D,
                 if ((int)rmax[1] > by1) rmax[1] = (uint32_t)(by1 < 0 ? 0 : by1);
                 if (rmax[0] <= rmin[0] || rmax[1] <= rmin[1]) continue;
                 per_tile = (rmax[0] - rmin[0]) >= 2 && (rmax[1] - rmin[1]) >= 2;
-                /* level 2 (round 6): rects of at most 4 tiles keep all their tiles (gs2m_rect_tested, raster_project.h) */
+                /* level 2 (round 6): rects of at most 4 tiles keep all their tiles (gs2m_rect_tested, raster_bin_walk.h) */
                 if (exact_cull == 2 && (rmax[0] - rmin[0]) * (rmax[1] - rmin[1]) <= 4) per_tile = 0;
             }
             if (rect_out) {

@@ -1117,3 +1117,180 @@ def test_flip_bounds_count_the_decisions_at_their_thresholds():
     co2 = np.array([[0.5, 0.0, 0.5, 0.99]] * 3, np.float32)
     fb2 = oracle.render_flip_bounds(W, H, np.array([[0, 3]], np.uint32), pl2, means2, co2, cmax=1.0, rel_eps=1e-5)
     assert fb2["n_T"][5, 5] >= 1 and fb2["bound"][5, 5] >= 0.009            # T = 0.01 in front of the deciding layer
+
+
+def _bin_rect_sizes(rect, rows):
+    """(w, h) in binning tiles of 16 x 16 * rows pixels of rects (x0, y0, x1, y1) in 16 x 16 tile units; (0, 0) for an empty one."""
+    q = np.asarray(rect).astype(np.int64)
+    w, h = q[:, 2] - q[:, 0], (q[:, 3] + rows - 1) // rows - q[:, 1] // rows
+    ok = (w > 0) & (q[:, 3] > q[:, 1])
+    return np.where(ok, w, 0), np.where(ok, h, 0)
+
+
+def _fold_tile_rows(pl, ranges, depths, gx, gy, rows):
+    """The oracle's 16 x 16-tile lists as lists of 16 x 16 * rows binning tiles: the Gaussians of the `rows` tiles under a binning
+    tile, each once, by ascending depth bits, ties by id (the order of the per-tile sort)."""
+    out_pl, out_ranges = [], []
+    n = 0
+    for ty in range((gy + rows - 1) // rows):
+        for tx in range(gx):
+            ids = np.unique(np.concatenate([pl[ranges[(ty * rows + k) * gx + tx, 0]:ranges[(ty * rows + k) * gx + tx, 1]]
+                                            for k in range(rows) if ty * rows + k < gy]))
+            ids = ids[np.argsort(depths[ids].view(np.uint32), kind="stable")]
+            out_pl.append(ids)
+            out_ranges.append((n, n + len(ids)))
+            n += len(ids)
+    return np.concatenate(out_pl).astype(np.uint32), np.asarray(out_ranges, np.uint32)
+
+
+@pytest.mark.parametrize("case", ["full_item_space", "one_past_staged", "class_borders"])
+def test_rects_on_the_borders_of_the_walk_classes(backend, case):
+    """k_count_tiles and k_scatter walk a rect by its class (raster_bin_walk.h): own lane (at most GS2M_OPT_BIN_LANE_TILES tiles, or
+    thin), staged item space (at most 64 tiles), whole wave (more).  Rects exactly ON the borders, checked present before anything is
+    compared:
+      full_item_space: 64 Gaussians whose rect is the whole 8 x 8 binning grid (128 x 128 pixels, and 128 x 256 with 16 x 32
+        tiles) -- every lane of the one wave step owns a 64-tile rect, w = h = 8, the last owner starts at item 4032 of 4096; with
+        the exact cull the rects are tested, half of them (diagonal needles) lose corners and bit 63 of the kept-tile mask is in
+        use.  Also as the two views of one launch (NV = 2): per view the lists of the single-view launch.
+      one_past_staged: the same at 144 x 128 -- 9 x 8 = 72 tiles, every lane takes the whole-wave walk.
+      class_borders: 1040 x 16, needles of 64 x 1 (staged) and 65 x 1 (whole wave) tiles; rects of exactly lane_max and
+        lane_max + 1 tiles at lane_max 4 (2 x 2, 4 x 1 | 5 x 1) and 16 (4 x 4, 16 x 1 | 17 x 1), the blobs on 128 x 128.
+    Cull 0: instance lists, ranges and count are the oracle's (with 16 x 32 tiles: the oracle's lists of the two tiles under a
+    binning tile, merged); cull 1, 2: the oracle's culled count, radii, image.  The oracle has no culled lists for 16 x 32 tiles:
+    there (full_item_space and one_past_staged, rows 2, cull 1 and 2) the count is only held between half the rect and all of
+    it, with the last tile in use; radii and image are compared as everywhere."""
+    be = backend
+    d = be.dev
+    rng = np.random.default_rng(808)
+
+    def camera(W, H, f=100.0, x=0.0):
+        return Camera(0, np.eye(3), np.array([x, 0, 4.0]), 2 * math.atan2(W, 2 * f), 2 * math.atan2(H, 2 * f), W, H)
+
+    def quat_z(a):
+        return np.stack([np.cos(a / 2), 0 * a, 0 * a, np.sin(a / 2)], axis=1).astype(np.float32)
+
+    def check(W, H, rows, cull, lane_tiles, xyz, s, q, o, cols, present):
+        cam = camera(W, H)
+        geom_ref = oracle.preprocess(xyz, s, q, o, None, cam.world_view_transform, cam.full_proj_transform, cam.camera_center, W, H,
+                                     cam.tanfovx, cam.tanfovy, colors_precomp=cols)
+        ref_pl, ref_ranges, rect = oracle.bin_instances(geom_ref, W, H, exact_cull=cull, want_rect=True)
+        w, h = _bin_rect_sizes(rect if cull else geom_ref["rect"], rows)
+        if cull == 0 and rows == 1:
+            np.testing.assert_array_equal(w * h, geom_ref["tiles_touched"])
+        present(w, h, cull)
+        r = Rasterizer(0, lib=be.lib)
+        r.set_option(_lib.OPT_EXACT_TILE_CULL, cull)
+        r.set_option(_lib.OPT_TILE_ROWS, rows)
+        if lane_tiles is not None:
+            r.set_option(_lib.OPT_BIN_LANE_TILES, lane_tiles)
+        img, radii = r.forward(d(xyz), d(o), d(cam.world_view_transform), d(cam.full_proj_transform), d(cam.camera_center),
+                               d(np.zeros(3, np.float32)), W, H, cam.tanfovx, cam.tanfovy, colors_precomp=d(cols), scales=d(s),
+                               rotations=d(q))
+        ref_img, ref_radii, ref_n = oracle_forward(cam, xyz, o, [0, 0, 0], colors_precomp=cols, scales=s, rotations=q, exact_cull=cull)
+        np.testing.assert_array_equal(be.host(radii), ref_radii)
+        gx, gy = (W + 15) // 16, (H + 15) // 16
+        n = r.last_num_rendered
+        pl, ranges = r.download_binning(0, n, gx * ((gy + rows - 1) // rows))
+        if cull == 0:
+            if rows > 1:
+                ref_pl, ref_ranges = _fold_tile_rows(ref_pl, ref_ranges, geom_ref["depths"], gx, gy, rows)
+            assert n == len(ref_pl) and (rows > 1 or n == ref_n)
+            np.testing.assert_array_equal(ranges, ref_ranges)
+            np.testing.assert_array_equal(pl, ref_pl)
+        elif rows == 1:
+            assert n == ref_n == len(ref_pl)
+        assert_image_close(be.host(img), ref_img)
+        return n, pl, ranges
+
+    if case in ("full_item_space", "one_past_staged"):
+        P = 64
+        xyz = np.zeros((P, 3), np.float32)
+        xyz[:, :2] = rng.uniform(-0.05, 0.05, (P, 2))
+        xyz[:, 2] = rng.permutation(P) * 0.006 - 0.2
+        s = np.full((P, 3), 3.0, np.float32)                        # even ids: blobs over the whole image
+        s[1::2] = [8.0, 0.5, 0.5]                                   # odd ids: needles along one of the diagonals
+        q = quat_z(np.where(np.arange(P) % 4 == 1, 1.0, -1.0) * np.where(np.arange(P) % 2 == 1, math.pi / 4, 0.0))
+        o = rng.uniform(0.3, 0.9, P).astype(np.float32)
+        o[::2] *= 0.1                                               # the image does not saturate under the first blob
+        o[::2] += 0.02
+        cols = rng.uniform(0, 1, (P, 3)).astype(np.float32)
+        side = 8 if case == "full_item_space" else 9
+        W = 16 * side
+
+        def present(w, h, cull):
+            assert (w == side).all() and (h == 8).all(), (w, h)      # every lane owns the whole grid: 64 (72) tiles
+
+        for rows in (1, 2):
+            n0 = None
+            for cull in (0, 1, 2):
+                n, pl, ranges = check(W, 128 * rows, rows, cull, None, xyz, s, q, o, cols, present)
+                if cull == 0:
+                    n0 = n
+                    assert n == P * side * 8
+                else:
+                    # tested rects: corners are cut, and the LAST tile of the rects (bit 63 of a 64-tile mask) is kept by some
+                    assert P * side * 8 // 2 < n < n0 and 0 < ranges[-1, 1] - ranges[-1, 0] < P
+        if case == "full_item_space":
+            # the two views of one launch (NV = 2): per view the lists of the one-view launch
+            H = 128
+            cams = [camera_from(camera(W, H)), camera_from(camera(W, H, x=0.02))]
+            gd = dict(xyz=d(xyz), scaling=d(s), rotation=d(q), opacity=d(o), raw=False, sh_degree=0,
+                      features=d(np.ascontiguousarray(cols[:, None, :])))
+            for cull in (0, 1):
+                def lists(cc):
+                    r = Rasterizer(0, lib=be.lib)
+                    r.set_option(_lib.OPT_EXACT_TILE_CULL, cull)
+                    res = r.render_views(gd, cc)
+                    return [(nv,) + r.download_binning(v, nv, 64) for v, nv in enumerate(res["num_rendered"])], be.host(res["color"]).copy()
+                pair, img_pair = lists(cams)
+                for v in range(2):
+                    one, img_one = lists(cams[v:v + 1])
+                    assert pair[v][0] == one[0][0] and (pair[v][0] == P * 64 if cull == 0 else P * 32 < pair[v][0] < P * 64)
+                    np.testing.assert_array_equal(pair[v][2], one[0][2])
+                    np.testing.assert_array_equal(pair[v][1], one[0][1])
+                    np.testing.assert_array_equal(img_pair[v], img_one[0])
+        return
+
+    # ---- class_borders: needles on a one-tile-high image
+    W, H = 1040, 16
+    widths = np.repeat([1, 3, 4, 5, 6, 15, 16, 17, 18, 62, 63, 64, 65], 6)       # aimed at; what comes out is checked below
+    P = len(widths)
+    left = np.array([rng.integers(0, 65 - wd + 1) for wd in widths])               # first tile of the rect
+    rad = np.maximum(widths * 8.0 - 8.0, 2.0)                                      # 3-sigma radius in pixels: spans `wd` tiles from mid-tile
+    mid = left * 16.0 + widths * 8.0 + rng.uniform(-3, 3, P)
+    xyz = np.zeros((P, 3), np.float32)
+    xyz[:, 0] = (mid - W / 2) * 4.0 / 100.0
+    xyz[:, 2] = rng.uniform(-0.02, 0.02, P)
+    s = np.full((P, 3), 0.002, np.float32)
+    s[:, 0] = rad / 3.0 * 4.0 / 100.0
+    q = np.tile([1, 0, 0, 0], (P, 1)).astype(np.float32)
+    o = rng.uniform(0.05, 0.6, P).astype(np.float32)
+    cols = rng.uniform(0, 1, (P, 3)).astype(np.float32)
+
+    def present_needles(w, h, cull):
+        assert (h[w > 0] == 1).all()
+        for wd in (4, 5, 16, 17, 64, 65):
+            assert (w == wd).any(), (wd, cull, np.bincount(w))
+
+    for lane_tiles in (None, 16):
+        for cull in (0, 1, 2):
+            check(W, H, 1, cull, lane_tiles, xyz, s, q, o, cols, present_needles)
+    # ---- and blobs of 2 x 2 and 4 x 4 tiles (exactly lane_max tiles at 4 and at 16) next to 3 x 3, 4 x 5, ...
+    W = H = 128
+    P = 160
+    xyz = np.zeros((P, 3), np.float32)
+    xyz[:, :2] = rng.uniform(-1.2, 1.2, (P, 2))
+    xyz[:, 2] = rng.uniform(-0.02, 0.02, P)
+    s = np.repeat(rng.uniform(0.05, 0.5, (P, 1)), 3, axis=1).astype(np.float32)
+    q = np.tile([1, 0, 0, 0], (P, 1)).astype(np.float32)
+    o = rng.uniform(0.05, 0.6, P).astype(np.float32)
+    cols = rng.uniform(0, 1, (P, 3)).astype(np.float32)
+
+    def present_blobs(w, h, cull):
+        for wd in (2, 4):
+            assert ((w == wd) & (h == wd)).any(), (wd, cull, np.bincount(w * h))
+        assert (w * h == 5).any() or (w * h == 6).any()
+
+    for lane_tiles in (None, 16):
+        for cull in (0, 1, 2):
+            check(W, H, 1, cull, lane_tiles, xyz, s, q, o, cols, present_blobs)
