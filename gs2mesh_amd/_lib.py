@@ -44,7 +44,15 @@ class AdamSegment(C.Structure):
                 ("row_width", C.c_int32), ("reserved", C.c_int32), ("lr", f64), ("beta1", f64), ("beta2", f64), ("eps", f64)]
 
 
+class DepthView(C.Structure):
+    """gs2m_depth_view (host struct of device pointers: one view of gs2m_depth_consistency)."""
+    _fields_ = [("depth", vp), ("mask", vp), ("width", C.c_int32), ("height", C.c_int32), ("fx", f32), ("fy", f32),
+                ("cx", f32), ("cy", f32)]
+
+
 ADAM_MAX_SEGMENTS = 8
+CONSISTENCY_MAX_SOURCES = 16
+CONSISTENCY_BATCH = 2       # reference views per launch of gs2m_depth_consistency
 ABI_VERSION = 600   # GS2M_VERSION of include/gs2mesh_amd.h this binding was written against
 OPT_EXACT_TILE_CULL = 1
 OPT_BLEND_VARIANT = 2
@@ -100,6 +108,8 @@ _PROTOS = {
     "gs2m_stereo_depth_occlusion": (i32, [vp, vp, i32, i32, f64, f64, vp, vp, vp]),
     "gs2m_stereo_sgm_scratch_bytes": (i64, [i32, i32, i32]),
     "gs2m_stereo_sgm": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp]),
+    "gs2m_depth_consistency": (i32, [i32, C.POINTER(DepthView), i32, C.POINTER(C.c_int32), C.POINTER(f32), f32, f32, f32, i32,
+                                     i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]),
     "gs2m_knn_scratch_bytes": (i64, [i32]),
     "gs2m_knn_mean_dist2": (i32, [i32, vp, vp, vp, i64, vp, vp]),
     "gs2m_nn_scratch_bytes": (i64, [i32, i32]),

@@ -3,6 +3,7 @@
 //   mask_kernels.h                    gs2m_mask_preprocess         the object / occlusion masks the TSDF integrates with
 //   mask_disk_kernels.h               gs2m_mask_dilate_disk        disk dilation on the same bitmaps (the DTU evaluation's cull)
 //   sgm_kernels.h                     gs2m_stereo_sgm              the built-in semi-global matcher
+//   depth_consistency_kernels.h       gs2m_depth_consistency       the cross-view vote on the depth maps, before they are fused
 //
 // Depth and occlusion are the small data-parallel step between the stereo matcher and the TSDF
 // (gs2mesh_utils/stereo_utils.py:132-133, 149-179).  Fused into one pass; outputs stay on the device and feed
@@ -27,6 +28,7 @@
 #include "mask_kernels.h"
 #include "mask_disk_kernels.h"
 #include "sgm_kernels.h"
+#include "depth_consistency_kernels.h"
 #include "api_check.h"
 
 GS2M_KERNEL void __launch_bounds__(256)
@@ -101,6 +103,92 @@ extern "C" int gs2m_mask_preprocess(int n, int width, int height, const uint8_t*
         unsigned long long* a_bits = scratch ? (unsigned long long*)scratch + 2 * (size_t)f0 * frame_words : nullptr;
         unsigned long long* b_bits = a_bits ? a_bits + (size_t)nf * frame_words : nullptr;
         gs2m_launch_mask_preprocess((hipStream_t)stream, B, nf, width, height, invert, erode, closing_k, erosion_k, a_bits, b_bits);
+    }
+    return 0;
+}
+
+extern "C" int gs2m_depth_consistency(int n_views, const gs2m_depth_view* views, int max_sources, const int32_t* sources,
+                                      const float* pair, float rel_tol, float min_depth, float max_depth, int min_support,
+                                      int max_violation, uint8_t* const* keep, uint8_t* const* support,
+                                      uint8_t* const* violation, uint8_t* const* occluded, gs2m_stream stream) {
+    static_assert(sizeof(ConsistencyBatch) <= 3072, "the descriptor table travels in the kernel argument segment");
+    const int K = max_sources;
+    if (n_views < 0 || K < 0 || K > DC_MAX_SOURCES) {
+        gs2m_set_error("gs2m_depth_consistency: n_views = %d, max_sources = %d (n_views >= 0, max_sources 0 .. %d)", n_views, K,
+                       DC_MAX_SOURCES);
+        return 1;
+    }
+    if (!(rel_tol > 0.0f && rel_tol < 1.0f)) {                                             // also refuses NaN
+        gs2m_set_error("gs2m_depth_consistency: rel_tol = %g must lie in (0, 1)", (double)rel_tol);
+        return 1;
+    }
+    if (n_views == 0) return 0;
+    if (!views || (K > 0 && (!sources || !pair))) {
+        gs2m_set_error("gs2m_depth_consistency: NULL views, sources or pair with n_views = %d, max_sources = %d", n_views, K);
+        return 1;
+    }
+    for (int i = 0; i < n_views; ++i) {
+        const gs2m_depth_view& V = views[i];
+        if (V.width <= 0 || V.height <= 0 || V.width > 65536 || V.height > 65536) {
+            gs2m_set_error("gs2m_depth_consistency: view %d is %d x %d (width and height 1 .. 65536)", i, V.width, V.height);
+            return 1;
+        }
+        if (!V.depth) {
+            gs2m_set_error("gs2m_depth_consistency: view %d has a NULL depth", i);
+            return 1;
+        }
+        for (int k = 0; k < K; ++k) {
+            const int j = sources[(size_t)i * K + k];
+            if (j == i || j < -1 || j >= n_views) {
+                gs2m_set_error("gs2m_depth_consistency: sources[%d][%d] = %d (another view in [0, %d), or -1 for none)", i, k, j,
+                               n_views);
+                return 1;
+            }
+        }
+    }
+    // every argument is good: from here on the call only launches
+    ConsistencyBatch B;
+    int nb = 0, gw = 0, gh = 0;
+    for (int i = 0; i < n_views; ++i) {
+        ConsistencyRef R;
+        memset(&R, 0, sizeof R);
+        R.keep = keep ? keep[i] : nullptr;
+        R.support = support ? support[i] : nullptr;
+        R.violation = violation ? violation[i] : nullptr;
+        R.occluded = occluded ? occluded[i] : nullptr;
+        const bool wanted = R.keep || R.support || R.violation || R.occluded;
+        if (wanted) {
+            const gs2m_depth_view& V = views[i];
+            R.depth = V.depth;
+            R.mask = V.mask;
+            R.W = V.width;
+            R.H = V.height;
+            R.fx = V.fx, R.fy = V.fy, R.cx = V.cx, R.cy = V.cy;
+            for (int k = 0; k < K; ++k) {                                                  // the -1 entries drop out here
+                const int j = sources[(size_t)i * K + k];
+                if (j < 0) continue;
+                ConsistencySource& S = B.src[nb][R.n_src++];
+                S.depth = views[j].depth;
+                S.mask = views[j].mask;
+                S.W = views[j].width;
+                S.H = views[j].height;
+                S.fx = views[j].fx, S.fy = views[j].fy, S.cx = views[j].cx, S.cy = views[j].cy;
+                memcpy(S.M, pair + ((size_t)i * K + k) * 12, sizeof S.M);
+            }
+            for (int k = R.n_src; k < DC_MAX_SOURCES; ++k) memset(&B.src[nb][k], 0, sizeof(ConsistencySource));
+            B.ref[nb++] = R;
+            gw = V.width > gw ? V.width : gw;
+            gh = V.height > gh ? V.height : gh;
+        }
+        if (nb == DC_BATCH || (nb > 0 && i == n_views - 1)) {
+            for (int b = nb; b < DC_BATCH; ++b) {                                          // unused slots: 0 x 0 views
+                memset(&B.ref[b], 0, sizeof(ConsistencyRef));
+                memset(B.src[b], 0, sizeof B.src[b]);
+            }
+            GS2M_LAUNCH(k_depth_consistency, dim3((gw + DC_PATCH_W - 1) / DC_PATCH_W, (gh + DC_PATCH_H - 1) / DC_PATCH_H, nb), dim3(256), 0,
+                        stream, B, rel_tol, min_depth, max_depth, min_support, max_violation);
+            nb = gw = gh = 0;
+        }
     }
     return 0;
 }

@@ -10,6 +10,10 @@ the host (scipy.ndimage; cv2 is not a dependency).  Frames can come from disk (`
 ``out_<model>/depth.npy``, ...: the reference layout, so ``--skip_rendering`` style resumes work) or
 from memory via ``frame_source`` (the in-memory hand-off).
 
+``TSDF(..., consistency=...)`` (or ``args.TSDF_consistency``) puts the cross-view test of ``depth_utils.depth_consistency`` in
+front of the fusion: the depth maps of all selected cameras vote on each other once, and each frame is then fused under its
+keep mask.  Off by default, and the reference has no such stage.
+
 ``TSDF(..., fuse="batch")`` (or ``args.TSDF_fuse = "batch"``) fuses the same frames into the same volume (every block, every
 voxel bit for bit) in sweeps of at most ``MAX_SWEEP`` frames: a thread pool reads the next sweep from disk while the current one is integrated,
 the masks of a sweep are preprocessed on the device in one call (``mask_preprocess``, ``gs2m_mask_preprocess``), the sweep
@@ -125,8 +129,10 @@ def mask_preprocess(object_masks, occlusion_masks=None, invert=False, erode=True
 class TSDF:
     MAX_SWEEP = 32          # frames per integrate_batch sweep of fuse="batch" (equal sweeps of at most this many)
     LOADER_THREADS = 8      # disk readers of fuse="batch" (capped by the CPUs this process may use)
+    CONSISTENCY_MAX_BYTES = 8 << 30     # consistency: all selected depth maps (and their masks) are resident at once, up to this
 
-    def __init__(self, renderer, stereo, args, out_name, frame_source=None, max_blocks=None, lib=None, fuse=None):
+    def __init__(self, renderer, stereo, args, out_name, frame_source=None, max_blocks=None, lib=None, fuse=None,
+                 consistency=None):
         self.model_name = stereo.model_name if stereo is not None else getattr(args, "stereo_model", "DLNR_Middlebury")
         self.renderer = renderer
         self.out_name = out_name
@@ -139,7 +145,14 @@ class TSDF:
         self.fuse = fuse if fuse is not None else getattr(args, "TSDF_fuse", "frame")
         if self.fuse not in ("frame", "batch"):
             raise ValueError(f"fuse must be 'frame' or 'batch', got {self.fuse!r}")
-        self.timings = {}       # wall seconds per stage of the last run(): fuse, extract, normals (+ load_wait, mask, integrate: batch)
+        self.timings = {}       # wall seconds per stage of the last run(): fuse, extract, normals (+ load_wait, mask, integrate: batch;
+                                # + consistency, a part of fuse, when the filter is on)
+        # the cross-view filter: a ConsistencyParams, a dict of its fields or True (the defaults); None = off.  Without the
+        # argument, args.TSDF_consistency (same forms) and args.TSDF_consistency_<field> say it; an args without them: off
+        self.consistency = self._consistency_params(consistency, args)
+        self._keep_masks = None     # during run(): camera number -> device keep mask
+        if self.consistency is not None:
+            self._consistency_bytes(self._selected())         # over the cap: refuse here, before anything is loaded
 
     def _load_frame(self, camera_number):
         if self.frame_source is not None:
@@ -181,6 +194,60 @@ class TSDF:
         extrinsic[:3, 3] /= self.args.TSDF_scale
         return np.linalg.inv(extrinsic)
 
+    @staticmethod
+    def _consistency_params(consistency, args):
+        import dataclasses
+        from .depth_utils import ConsistencyParams
+        if consistency is not None:
+            return ConsistencyParams.coerce(consistency)
+        p = ConsistencyParams.coerce(getattr(args, "TSDF_consistency", None))
+        if p is None:
+            return None
+        over = {f.name: getattr(args, "TSDF_consistency_" + f.name) for f in dataclasses.fields(ConsistencyParams)
+                if getattr(args, "TSDF_consistency_" + f.name, None) is not None}
+        return dataclasses.replace(p, **over) if over else p
+
+    def _consistency_bytes(self, cameras):
+        """bytes the filter keeps on the device for ``cameras``: depth f32 + keep u8 (+ occlusion u8) per pixel"""
+        per_pixel = 4 + 1 + (1 if self.args.TSDF_use_occlusion_mask else 0)
+        need = sum(per_pixel * int(self.renderer.left_cameras[c]['width']) * int(self.renderer.left_cameras[c]['height'])
+                   for c in cameras)
+        if need > int(self.CONSISTENCY_MAX_BYTES):
+            raise RuntimeError(f"TSDF consistency: the {len(cameras)} selected depth maps need {need} bytes on the device at once, "
+                               f"above TSDF.CONSISTENCY_MAX_BYTES = {int(self.CONSISTENCY_MAX_BYTES)}; fuse fewer views (TSDF_dilate / "
+                               "TSDF_valid / TSDF_skip), raise the cap or run without consistency (there is no windowed mode)")
+        return need
+
+    def _consistency_keep(self, volume):
+        """camera number -> device u8 keep mask (``depth_utils.depth_consistency``) over the depth maps of ``_selected()``, one
+        call.  A pixel has a depth where ``run`` would fuse it: inside the min / max depth range (unscaled units) and, with
+        TSDF_use_occlusion_mask, on the frame's occlusion mask -- so a keep mask lies inside the occlusion mask and stands in
+        for it when the frame is fused.  Disk frames are read here for their depth and occlusion mask and again by the fusion."""
+        from .depth_utils import depth_consistency
+        t0 = time.perf_counter()
+        a = self.args
+        cams = self._selected()
+        self._consistency_bytes(cams)
+        depths, occs, intr = [], [], []
+        for c in cams:
+            fr = self._load_frame(c)
+            i = self._intrinsic(c)
+            if tuple(fr["depth"].shape) != (i.height, i.width):
+                raise RuntimeError("[ScalableTSDFVolume::Integrate] Unsupported image format.")
+            depths.append(fr["depth"])
+            occs.append(fr.get("occlusion") if a.TSDF_use_occlusion_mask else None)
+            intr.append(i)
+        poses = np.stack([np.asarray(self.renderer.left_cameras[c]['extrinsic'], np.float64) for c in cams]) if cams else \
+            np.zeros((0, 4, 4))
+        baseline = self.renderer.baseline
+        keep = depth_consistency(depths, intr, poses, self.consistency, masks=occs if any(o is not None for o in occs) else None,
+                                 min_depth=a.TSDF_min_depth_baselines * baseline, max_depth=a.TSDF_max_depth_baselines * baseline,
+                                 lib=volume._lib, device=volume.device)
+        # host wall time of getting the frames and queueing the one call; the kernels' own time is not in it (nothing waits
+        # for them here): it shows in whatever synchronises next, and tools/consistency_bench.py measures it with events
+        self._consistency_time = time.perf_counter() - t0
+        return dict(zip(cams, keep))
+
     def _sweeps(self, cameras):
         """consecutive cameras sharing one intrinsic, cut into equal sweeps of at most MAX_SWEEP (bench.py's rule)"""
         groups = []
@@ -206,17 +273,29 @@ class TSDF:
             kw["lib"] = self._lib
         volume = ScalableTSDFVolume(voxel_length=float(voxel_length), sdf_trunc=a.TSDF_sdf_trunc,
                                     color_type=TSDFVolumeColorType.RGB8, **kw)
+        if self.consistency is not None:
+            try:
+                self._keep_masks = self._consistency_keep(volume)
+                return self._fuse(volume)
+            finally:                                    # also when a frame fails to load: the device masks do not outlive run()
+                self._keep_masks = None
+        return self._fuse(volume)
+
+    def _fuse(self, volume):
+        a = self.args
         baseline = self.renderer.baseline
         if self.fuse == "batch":
             self._fuse_batch(volume)
             return self._finish(volume, on_device=True)
         for camera_number in self._selected():
             fr = self._load_frame(camera_number)
+            if self._keep_masks is not None:                  # the keep mask lies inside the occlusion mask: it takes its place
+                fr = dict(fr, occlusion=_lib.MEMORY.download(self._keep_masks[camera_number]))
             mask = None
             if a.TSDF_use_mask and fr.get("mask") is not None:
                 mask = preprocess_object_mask(fr["mask"], a.TSDF_invert_mask, a.TSDF_erode_mask,
                                               a.TSDF_closing_kernel_size, a.TSDF_erosion_kernel_size)
-            if a.TSDF_use_occlusion_mask and fr.get("occlusion") is not None:
+            if (a.TSDF_use_occlusion_mask or self._keep_masks is not None) and fr.get("occlusion") is not None:
                 occ = fr["occlusion"]
                 occ = np.asarray(occ.cpu() if hasattr(occ, "cpu") else occ).astype(bool)
                 mask = occ if mask is None else (np.asarray(mask).astype(bool) & occ)
@@ -245,6 +324,8 @@ class TSDF:
             self.mesh.compute_vertex_normals()                      # :110
         t2 = time.perf_counter()
         self.timings.update(extract=t1 - t0, normals=t2 - t1)
+        if self._keep_masks is not None:
+            self.timings["consistency"] = self._consistency_time
 
     def _fuse_batch(self, volume):
         """fuse="batch": the frames of ``_selected()`` in order, sweep by sweep.  Disk frames are read by a thread pool one sweep
@@ -287,6 +368,8 @@ class TSDF:
                                                                 convert_rgb_to_intensity=False))
             objs.append(fr.get("mask") if a.TSDF_use_mask else None)
             occs.append(fr.get("occlusion") if a.TSDF_use_occlusion_mask else None)
+        if self._keep_masks is not None:                      # a keep mask lies inside its frame's occlusion mask: it takes its place
+            occs = [self._keep_masks[c] for c in cams]
         t0 = time.perf_counter()
         masks = None
         if any(m is not None for m in objs + occs):

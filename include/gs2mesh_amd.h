@@ -38,7 +38,7 @@ extern "C" {
                             removed).  Added since without a new number: gs2m_stereo_sgm / gs2m_stereo_sgm_scratch_bytes,
                             gs2m_knn_mean_dist2 / gs2m_knn_scratch_bytes, gs2m_photo_loss_forward / _backward /
                             _scratch_bytes, gs2m_adam_step, gs2m_densify_stats, gs2m_icp_prepare / _step / _scratch_bytes,
-                            gs2m_voxel_mean.  The Python binding checks it at load time */
+                            gs2m_voxel_mean, gs2m_depth_consistency.  The Python binding checks it at load time */
 
 typedef void* gs2m_stream; /* hipStream_t */
 
@@ -716,6 +716,54 @@ int gs2m_mask_dilate_disk(int n, int width, int height, const uint8_t* const* ma
 int64_t gs2m_stereo_sgm_scratch_bytes(int width, int height, int max_disparity);
 int gs2m_stereo_sgm(const uint8_t* left_rgb8, const uint8_t* right_rgb8, int width, int height, int max_disparity, int p1, int p2,
                     float* disp_lr, float* disp_rl, void* scratch, int64_t scratch_bytes, uint16_t* tap_cost_lr, gs2m_stream stream);
+
+/*
+ * The cross-view test between the depth stage and the TSDF: every pixel of every view votes with up to 16 other views
+ * ("sources") on whether its depth is a surface they see too.  What depth-map fusion pipelines run before they fuse
+ * (COLMAP's geometric consistency, the MVSNet family's filter); the reference has no such stage, so there is nothing to be
+ * compatible with and the arithmetic below IS the definition.  In f32, every operation rounded on its own (no FMA, IEEE
+ * division), parentheses = order.
+ *   valid(view, y, x)  <=>  d = depth[y][x] satisfies d > 0 && d >= min_depth && d < max_depth  (false for NaN; max_depth =
+ *                           +inf excludes only the infinities)  and  (mask == NULL || mask[y][x] != 0)
+ * For reference view i, pixel (u, v) with valid(i, v, u), d its depth, and each k < max_sources with j = sources[i][k] >= 0,
+ * M = pair[i][k]:
+ *   x = (((float)u - cx_i) * d) / fx_i,  y = (((float)v - cy_i) * d) / fy_i,  z = d
+ *   q_r = ((M[r][0] * x + M[r][1] * y) + M[r][2] * z) + M[r][3],  r = 0, 1, 2
+ *   !(q_2 > 0): no vote
+ *   pu = ((q_0 * fx_j) / q_2 + cx_j) + 0.5f,  pv = ((q_1 * fy_j) / q_2 + cy_j) + 0.5f
+ *   !(pu >= 0 && pu < (float)W_j && pv >= 0 && pv < (float)H_j): no vote
+ *   iu = (int)floorf(pu), iv = (int)floorf(pv)         (pixel centres at integers: the convention of gs2m_tsdf_integrate)
+ *   !valid(j, iv, iu): no vote
+ *   diff = depth_j[iv][iu] - q_2,  tol = rel_tol * q_2
+ *   fabsf(diff) <= tol: support;  else diff > tol: violation (the source sees past the point: it lies in the source's
+ *   observed free space);  else: occluded (the source sees something in front: no evidence either way)
+ *   keep = valid(i, v, u) && support >= min_support && violation <= max_violation
+ * A pixel that is not valid gets keep = 0 and zero counts.  The same source named twice votes twice.
+ *   views                   host array [n_views] of gs2m_depth_view (device pointers); sizes and intrinsics may differ from
+ *                           view to view; width and height in 1 .. 65536
+ *   max_sources             K, 0 .. 16
+ *   sources                 host [n_views][K] int32: index of a source view, -1 = none (anywhere in a row)
+ *   pair                    host [n_views][K][12] f32: row-major 3 x 4, reference camera -> source camera (rows of -1 entries
+ *                           are not read)
+ *   rel_tol                 in (0, 1)
+ *   keep, support, violation, occluded
+ *                           host arrays [n_views] of [height][width] u8 DEVICE pointers; an array or an entry may be NULL
+ *                           (not written); a view none of whose four outputs is asked for costs nothing
+ * The host arrays are consumed before the call returns: the descriptors travel as kernel arguments, two reference views per
+ * launch.  n_views = 0 does nothing and returns 0.  Stateless, asynchronous on `stream`, no allocation, no atomics, the same
+ * bits on every run.  Bad arguments return 1 with gs2m_last_error() and nothing is written: sources[i][k] == i, an index
+ * >= n_views or < -1, max_sources > 16, rel_tol outside (0, 1), a view of non-positive (or too large a) size, a NULL depth.
+ */
+typedef struct gs2m_depth_view { /* host struct, device pointers */
+    const float* depth;          /* [height][width] f32 */
+    const uint8_t* mask;         /* NULL, or [height][width] u8: 0 = this pixel has no depth */
+    int32_t width, height;
+    float fx, fy, cx, cy;
+} gs2m_depth_view;
+int gs2m_depth_consistency(int n_views, const gs2m_depth_view* views, int max_sources, const int32_t* sources, const float* pair,
+                           float rel_tol, float min_depth, float max_depth, int min_support, int max_violation,
+                           uint8_t* const* keep, uint8_t* const* support, uint8_t* const* violation, uint8_t* const* occluded,
+                           gs2m_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* nearest neighbours (simple-knn's distCUDA2, the initial scales of 3DGS training)     */
