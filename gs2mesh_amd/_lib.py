@@ -91,6 +91,7 @@ _PROTOS = {
                                             f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "gs2m_raster_backward_rows": (i32, [vp, C.POINTER(i64), C.POINTER(i64)]),
     "gs2m_rasterize_depth": (i32, [vp, i32, i32, vp, vp, vp, vp]),
+    "gs2m_rasterize_depth_ray": (i32, [vp, i32, vp, vp, f32, vp, vp, f32, f32, i32, i32, vp, vp, vp, vp]),
     "gs2m_mark_visible": (i32, [i32, vp, vp, vp, vp, vp]),
     "gs2m_render_views": (i32, [vp, C.POINTER(Gaussians), C.POINTER(Camera), i32, C.POINTER(f32), f32, vp, vp, vp,
                                 vp]),

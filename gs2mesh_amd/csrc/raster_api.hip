@@ -69,6 +69,7 @@ struct gs2m_raster {
     DeviceBuffer<unsigned> d_bw_blocks;     // [ceil(P / 256)] scan scratch
     DeviceBuffer<unsigned long long> d_bw_total;   // [1]
     unsigned long long bw_last_rows = 0;  // instance rows of the last backward call
+    DeviceBuffer<float4> d_ray;           // [P][4] ray records of gs2m_rasterize_depth_ray (raster_depth_ray.h), grow-only
     bool fw_valid = false;               // the state is that of ONE gs2m_rasterize_forward call
     int fw_P = 0, fw_W = 0, fw_H = 0, fw_tile_rows = 1;
     // last call
@@ -652,6 +653,51 @@ extern "C" int gs2m_rasterize_depth(gs2m_raster* r, int width, int height, float
     gs2m_launch_blend_depth(st, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, P, r->last_cap, width, height, depth_expected,
                             depth_median, alpha);
     if (dbg_check(r, st, "blend depth")) return 1;
+    return 0;
+}
+
+// The same maps with the ray-Gaussian intersection depth of every (instance, pixel) where gs2m_rasterize_depth has the centre's z
+// (raster_depth_ray.h): a record pass over the Gaussians from the forward's inputs, then the same walk.  Reads the forward state
+// and writes the handle's ray records only, so a gs2m_rasterize_backward or a gs2m_rasterize_depth may follow.  No host wait
+// once the record array has its size (grow-only, [P] records of 64 bytes).
+extern "C" int gs2m_rasterize_depth_ray(gs2m_raster* r, int P, const float* means3D, const float* scales, float scale_modifier,
+                                        const float* rotations, const float* viewmatrix, float tanfovx, float tanfovy, int width,
+                                        int height, float* depth_expected, float* depth_median, float* alpha,
+                                        gs2m_stream stream) {
+    const char* who = "gs2m_rasterize_depth_ray";
+    if (!r) {
+        gs2m_set_error("null handle");
+        return 1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    GS2M_HIPCHK(hipSetDevice(r->device));
+    if (check_forward_state(r, who, width, height, &P)) return 1;
+    const size_t bytes = sizeof(float) * (size_t)width * height;
+    if (r->fw_P == 0) {   // the forward rendered nothing: no pixel has a contributor
+        if (depth_expected) GS2M_HIPCHK(hipMemsetAsync(depth_expected, 0, bytes, st));
+        if (depth_median) GS2M_HIPCHK(hipMemsetAsync(depth_median, 0, bytes, st));
+        if (alpha) GS2M_HIPCHK(hipMemsetAsync(alpha, 0, bytes, st));
+        return 0;
+    }
+    if (!means3D || !scales || !rotations || !viewmatrix) {
+        gs2m_set_error("%s: NULL means3D / scales / rotations / viewmatrix (a forward with cov3D_precomp has no ray depth: "
+                       "the intersection needs the factors of the covariance)", who);
+        return 1;
+    }
+    if (r->h_status.get()[1].overflow) {
+        gs2m_set_error("%s: the forward overflowed its instance arena (gs2m_raster_status / gs2m_raster_reserve, then run it again)", who);
+        return 1;
+    }
+    if (!depth_expected && !depth_median && !alpha) return 0;
+    int gx, gy;
+    tile_grid(width, height, &gx, &gy);
+    const GeomRecs recs{r->d_recs.get(), r->d_recs.get() + 2 * (size_t)P};
+    if (r->d_ray.reserve((size_t)P * 4)) return 1;
+    gs2m_launch_ray_records(st, recs, P, means3D, scales, scale_modifier, rotations, viewmatrix, r->d_ray.get());
+    if (dbg_check(r, st, "ray records")) return 1;
+    gs2m_launch_blend_depth_ray(st, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, P, r->last_cap, width, height,
+                                r->d_ray.get(), tanfovx, tanfovy, depth_expected, depth_median, alpha);
+    if (dbg_check(r, st, "blend depth ray")) return 1;
     return 0;
 }
 

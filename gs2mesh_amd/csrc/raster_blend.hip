@@ -69,5 +69,21 @@ void gs2m_launch_blend_depth(hipStream_t st, int gx, int gy, const unsigned long
                              float* alpha) {
     const int tiles = gx * gy;
     GS2M_LAUNCH((k_blend_depth<4>), dim3((tiles + 3) / 4), dim3(256), 0, st, keys, tile_start, recs, P, cap, W, H, gx, gy,
-                depth_expected, depth_median, alpha);
+                depth_expected, depth_median, alpha, (const float4*)nullptr, 0.0f, 0.0f);
+}
+
+// ray records of the Gaussians the last forward listed (raster_depth_ray.h): one lane per Gaussian
+void gs2m_launch_ray_records(hipStream_t st, GeomRecs recs, int P, const float* means3D, const float* scales, float scale_modifier,
+                             const float* rotations, const float* viewmatrix, float4* ray) {
+    GS2M_LAUNCH(k_ray_records, dim3((P + 255) / 256), dim3(256), 0, st, recs, P, means3D, scales, scale_modifier, rotations,
+                viewmatrix, ray);
+}
+
+// the walk of gs2m_launch_blend_depth with the ray-Gaussian intersection depth of every (instance, pixel)
+void gs2m_launch_blend_depth_ray(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
+                                 GeomRecs recs, int P, unsigned cap, int W, int H, const float4* ray, float tanfovx,
+                                 float tanfovy, float* depth_expected, float* depth_median, float* alpha) {
+    const int tiles = gx * gy;
+    GS2M_LAUNCH((k_blend_depth<4, true>), dim3((tiles + 3) / 4), dim3(256), 0, st, keys, tile_start, recs, P, cap, W, H, gx, gy,
+                depth_expected, depth_median, alpha, ray, tanfovx, tanfovy);
 }

@@ -72,3 +72,9 @@ void gs2m_launch_gaussian_backward(hipStream_t st, const GaussIn& g, const CamUn
 void gs2m_launch_blend_depth(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
                              GeomRecs recs, int P, unsigned cap, int W, int H, float* depth_expected, float* depth_median,
                              float* alpha);
+// ---- ray-Gaussian intersection depth (gs2m_rasterize_depth_ray): ray[P][4] float4, written for the Gaussians with a tile rect
+void gs2m_launch_ray_records(hipStream_t st, GeomRecs recs, int P, const float* means3D, const float* scales, float scale_modifier,
+                             const float* rotations, const float* viewmatrix, float4* ray);
+void gs2m_launch_blend_depth_ray(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
+                                 GeomRecs recs, int P, unsigned cap, int W, int H, const float4* ray, float tanfovx,
+                                 float tanfovy, float* depth_expected, float* depth_median, float* alpha);

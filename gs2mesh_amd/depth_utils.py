@@ -11,6 +11,10 @@ and opacity come from the same call:
   * ``kind="median"`` (default): z of the contributor that takes the transmittance to one half or below -- a z some Gaussian
     really has, 0 where the accumulated opacity stays under 0.5;
   * ``kind="expected"``: the alpha-weighted mean z of the contributors -- smooth, but between the layers where two overlap;
+  * ``kind="ray_median"`` / ``"ray_expected"``: the same two with the depth at which the pixel's ray meets each contributing
+    Gaussian in place of its centre's z (``gs2m_rasterize_depth_ray``, one more kernel pair per view): the plane of a flat
+    Gaussian instead of a staircase on every surface that is not fronto-parallel -- the baseline the depth-from-splat meshers
+    (2DGS, GOF, RaDe-GS) fuse.  Isotropic Gaussians carry no orientation and gain nothing;
   * the occlusion mask of the layout is ``alpha >= alpha_min``: a free foreground mask where no object masker exists.
 No gradient flows through any of it.
 
@@ -30,7 +34,7 @@ import numpy as np
 from . import _lib
 from .stereo_utils import _ViewWriter
 
-KINDS = {"median": "median_depth", "expected": "depth"}
+KINDS = {"median": "median_depth", "expected": "depth", "ray_median": "ray_median_depth", "ray_expected": "ray_depth"}
 
 
 def select_sources(camera_to_world, k=4, max_angle_deg=70.0):
@@ -222,7 +226,8 @@ class RenderedDepth:
         from .gaussian_renderer import render
         cam, gaussians, background = self.renderer.left_view(camera_number)
         with torch.no_grad():
-            out = render(cam, gaussians, getattr(self.args, "pipe", None), background, return_depth=True)
+            out = render(cam, gaussians, getattr(self.args, "pipe", None), background, return_depth=True,
+                         ray_depth=self.kind.startswith("ray_"))
             # the 8-bit image as torchvision's save_image quantises it (the reference's left.png)
             image = out["render"].clamp(0.0, 1.0).mul(255.0).add_(0.5).clamp_(0.0, 255.0).to(torch.uint8)
             image = image.permute(1, 2, 0).contiguous()

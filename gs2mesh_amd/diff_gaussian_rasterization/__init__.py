@@ -265,14 +265,36 @@ class GaussianRasterizer(nn.Module):
         contributor that takes the transmittance to 0.5 or below) and ``alpha`` (accumulated opacity); 0 = no contributor
         (``gs2m_rasterize_depth``).  If another forward ran on the device's handle since, this one is replayed first into a
         scratch image, the way the backward pass does.  The results are DETACHED; maps that carry the graph come from
-        ``forward(..., return_depth=True)``."""
+        ``forward(..., return_depth=True)``.
+
+        ``expected_ray`` and ``median_ray`` are the same two maps with the depth at which the pixel's ray meets each
+        contributing Gaussian in place of its centre's z (``gs2m_rasterize_depth_ray``: one more call, from the inputs of the
+        last forward).  They need ``scales`` and ``rotations``: after a forward with ``cov3D_precomp`` asking for them raises
+        ``ValueError``.  No gradient flows through them."""
+        names = ("expected", "median", "alpha")
+        ray_names = {"expected_ray": "expected", "median_ray": "median"}
         if self._last is None:
             raise RuntimeError("GaussianRasterizer.depth_maps: this rasteriser has not run a forward")
+        unknown = [w for w in want if w not in names and w not in ray_names]
+        if unknown:
+            raise ValueError(f"depth_maps: unknown map(s) {unknown}; known: {names + tuple(ray_names)}")
         h, calls, inputs = self._last
         rs = self.raster_settings
+        means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp = inputs
+        want_ray = tuple(ray_names[w] for w in ray_names if w in want)
+        if want_ray and (scales.numel() == 0 or rotations.numel() == 0):
+            raise ValueError("GaussianRasterizer.depth_maps: expected_ray / median_ray need scales and rotations; the last "
+                             "forward took cov3D_precomp, which has no ray depth")
         with torch.no_grad():
             if h.state_calls != calls:
-                means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp = inputs
                 _forward(h, rs, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)
                 self._last = (h, h.state_calls, inputs)
-            return h.depth_maps(int(rs.image_width), int(rs.image_height), want=want, like=_f32c(rs.bg))
+            W, H = int(rs.image_width), int(rs.image_height)
+            out = h.depth_maps(W, H, want=tuple(w for w in want if w in names), like=_f32c(rs.bg)) \
+                if any(w in names for w in want) else {}
+            if want_ray:
+                ray = h.depth_maps_ray(_f32c(means3D), _f32c(scales), _f32c(rotations), _f32c(rs.viewmatrix), W, H,
+                                       float(rs.tanfovx), float(rs.tanfovy), scale_modifier=float(rs.scale_modifier),
+                                       want=want_ray, like=_f32c(rs.bg))
+                out.update({w: ray[k] for w, k in ray_names.items() if w in want})
+            return out

@@ -18,13 +18,17 @@ def _dev(x, device):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, return_depth=False,
-           depth_grad=False):
+           depth_grad=False, ray_depth=False):
     """Background tensor (bg_color) must be on the GPU, as in the reference.  ``return_depth=True`` (an extension: the reference
     renders colour only) adds three [H,W] maps of the same forward to the dict: ``depth`` (alpha-weighted mean
     view-space z of the contributing Gaussians' centres), ``median_depth`` (z of the contributor that takes the transmittance
     to one half) and ``alpha`` (accumulated opacity; render = C + (1 - alpha) * bg); 0 = no contributor.  They are detached
     unless ``depth_grad=True``: then, where gradients are wanted, they carry the graph (``gs2m_rasterize_backward_depth``) and
-    a loss on them trains the splat; ``viewspace_points.grad`` then includes their screen-space term."""
+    a loss on them trains the splat; ``viewspace_points.grad`` then includes their screen-space term.
+    ``ray_depth=True`` (with ``return_depth``) adds ``ray_depth`` and ``ray_median_depth``: the same two depth maps with the
+    depth at which the pixel's ray meets each contributing Gaussian in place of its centre's z (``gs2m_rasterize_depth_ray``) --
+    the plane of a flat Gaussian instead of a staircase.  These two are always DETACHED, also with ``depth_grad=True``, which
+    leaves the other maps and their gradients as they are.  Not available with ``pipe.compute_cov3D_python``."""
     device = pc.get_xyz.device
     tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
     tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
@@ -82,4 +86,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         if maps is None:
             maps = rasterizer.depth_maps()
         out.update(depth=maps["expected"], median_depth=maps["median"], alpha=maps["alpha"])
+        if ray_depth:
+            ray = rasterizer.depth_maps(want=("expected_ray", "median_ray"))
+            out.update(ray_depth=ray["expected_ray"], ray_median_depth=ray["median_ray"])
     return out

@@ -270,6 +270,32 @@ class Rasterizer:
                                                   _ptr(out.get("alpha")), st), self._lib)
         return out
 
+    def depth_maps_ray(self, means3D, scales, rotations, viewmatrix, W, H, tanfovx, tanfovy, scale_modifier=1.0,
+                       want=("expected", "median", "alpha"), like=None, stream=None):
+        """``gs2m_rasterize_depth_ray``: the maps of ``depth_maps`` with the depth at which the pixel's ray meets each
+        contributing Gaussian (the maximum of its density along the ray; the ray-plane intersection for a flat one) where
+        ``depth_maps`` has the z of its centre.  Maps of the LAST ``forward`` on this handle, whose ``means3D``, ``scales``,
+        ``rotations``, ``viewmatrix``, ``scale_modifier`` and camera these must be; a forward with ``cov3D_precomp`` has no ray
+        depth.  ``alpha`` has the bits of ``depth_maps``' alpha.  -> dict of freshly allocated [H,W] float32 arrays, one per
+        name in ``want``; 0 = no contributor.  Asynchronous; no gradients.  ``like``: a tensor on the device the maps go to
+        (default: where ``means3D`` lives)."""
+        names = ("expected", "median", "alpha")
+        unknown = [w for w in want if w not in names]
+        if unknown:
+            raise ValueError(f"depth_maps_ray: unknown map(s) {unknown}; known: {names}")
+        if scales is None or rotations is None:
+            raise ValueError("depth_maps_ray needs scales and rotations: a forward with cov3D_precomp has no ray depth")
+        like = means3D if like is None else like
+        shape = (int(H), int(W))
+        out = {k: _empty(like, shape, np.float32) for k in names if k in want}
+        st = _stream_of(like, stream)
+        f32 = torch.float32 if _is_torch(means3D) else None
+        _lib.check(self._lib.gs2m_rasterize_depth_ray(
+            self._h, int(means3D.shape[0]), _ptr(means3D, f32, "means3D"), _ptr(scales, f32, "scales"), float(scale_modifier),
+            _ptr(rotations, f32, "rotations"), _ptr(viewmatrix, f32, "viewmatrix"), float(tanfovx), float(tanfovy), int(W), int(H),
+            _ptr(out.get("expected")), _ptr(out.get("median")), _ptr(out.get("alpha")), st), self._lib)
+        return out
+
     def backward_rows(self):
         """-> (instance rows of the last ``backward``, bytes of the handle's row arena; 0 = never allocated)."""
         rows, nbytes = C.c_int64(0), C.c_int64(0)

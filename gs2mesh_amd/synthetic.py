@@ -279,3 +279,21 @@ def textured_sphere(P, seed, radius=0.6, sigma=0.02):
     f_dc = RGB2SH(rng.uniform(0, 1, size=(P, 1, 3))).astype(np.float32)
     return dict(xyz=xyz, features_dc=f_dc, features_rest=np.zeros((P, 15, 3), np.float32), scaling=scaling,
                 rotation=rotation, opacity=opacity)
+
+
+def surfel_sphere(P, seed, radius=0.6, sigma=0.03, thickness=1e-4):
+    """``textured_sphere`` with FLAT discs: P opaque splats of scales (sigma, sigma, thickness) on the sphere of ``radius``,
+    each rotated so that its thin axis is the sphere's normal at its centre -- a splat that carries the surface's orientation,
+    as a trained one does.  The tangent plane of a disc of radius 3 sigma leaves the sphere by about (3 sigma)^2 / (2 radius)."""
+    rng = np.random.default_rng(seed)
+    g = textured_sphere(P, seed, radius, sigma)
+    n = g["xyz"].astype(np.float64) / radius
+    # the shortest rotation that takes +z to n: q = (1 + n_z, -n_y, n_x, 0), normalised (n = -z: a half turn about x)
+    q = np.stack([1.0 + n[:, 2], -n[:, 1], n[:, 0], np.zeros(P)], axis=1)
+    flip = np.linalg.norm(q, axis=1) < 1e-6
+    q[flip] = [0.0, 1.0, 0.0, 0.0]
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    g["rotation"] = q.astype(np.float32)
+    g["scaling"] = np.log(np.tile(np.array([sigma, sigma, thickness]), (P, 1))).astype(np.float32)
+    g["features_dc"] = RGB2SH(rng.uniform(0, 1, size=(P, 1, 3))).astype(np.float32)
+    return g

@@ -300,6 +300,62 @@ int gs2m_raster_backward_rows(gs2m_raster* r, int64_t* rows, int64_t* arena_byte
 int gs2m_rasterize_depth(gs2m_raster* r, int width, int height, float* depth_expected, float* depth_median,
                          float* alpha, gs2m_stream stream);
 
+/*
+ * The maps of gs2m_rasterize_depth with the RAY-GAUSSIAN INTERSECTION depth of every (instance, pixel) where that call has the
+ * z of the centre (csrc/raster_depth_ray.h).  The centre's z is wrong wherever a surface is not fronto-parallel: a flat
+ * Gaussian on a tilted surface covers pixels whose rays meet it nearer or farther than its centre, and the map is a staircase.
+ * Produces the maps of the LAST gs2m_rasterize_forward on this handle, whose inputs P, means3D, scales, scale_modifier,
+ * rotations, viewmatrix, tanfovx, tanfovy, width and height must be (the convention of gs2m_rasterize_backward).
+ *
+ * For Gaussian j: W = the upper 3 x 3 of the view matrix as computeCov2D reads it (W[i][k] = viewmatrix[4 k + i]), mu = its
+ * view-space mean (transformPoint4x3), s = scale_modifier * scales[j], R(q) = the rotation matrix as computeCov3D forms it from
+ * rotations[j], used as given (unit quaternions are assumed), M = W R.  The maximum of the Gaussian's density along the pixel's
+ * ray x = t r (r_z = 1, so t is a view-space depth) is t* = (r^T B mu) / (r^T B r) for B ANY positive multiple of
+ * adj(Sigma_view); the adjugate exists for a singular Sigma, so a disc of zero thickness gives exactly the ray-plane
+ * intersection (n . mu) / (n . r).  In factors, without cancellation between terms and without 2 x 2 minors:
+ *     g = (s1 s2, s0 s2, s0 s1);  gmax = max g_k
+ *     if !(gmax > 0) or gmax not finite:  w_k = 0, c_k = 0      (rank <= 1: no orientation)
+ *     else  w_k = (g_k / gmax) * (column k of M),  c_k = w_k . mu        k = 0, 1, 2
+ *     sz  = sqrt(max(sum_k s_k^2 M[2][k]^2, 0))     (fmaxf semantics: a NaN counts as 0)
+ *     lo  = max(z_c - 4 sz, 0.2),  hi = z_c + 4 sz   (z_c = the view depth of the forward's record, the sort key's)
+ * and per (instance, pixel), px, py the integer pixel coordinates:
+ *     r   = (((2 px + 1) / W - 1) tanfovx, ((2 py + 1) / H - 1) tanfovy, 1)     (the inverse of ndc2Pix: pixel centres at integers)
+ *     u_k = w_k . r;  num = sum_k c_k u_k;  den = sum_k u_k^2
+ *     t   = (den > 0 and num / den is finite) ? num / den : z_c
+ *     z_j(p) = min(max(t, lo), hi)
+ * The walk is that of gs2m_rasterize_depth, unchanged -- the same alpha, the same three decisions, the same S / Z / median rule
+ * -- with z_j(p) where z_j stood: Z = fma(w, z_j(p), Z), and the median is z_j(p) of the first contributor that takes T to 0.5
+ * or below.  The clamp is exact for every ray that passes within 4 sigma of the centre (the maximum along such a ray lies inside
+ * that ellipsoid); it bounds what an edge-on disc, visible only through the 0.3 px dilation, can contribute.  By construction
+ * every z_j(p) is finite and in [lo, hi] within [0.2, inf) for a finite z_c, 0 still means "no depth", and alpha does not depend
+ * on z at all: it has the bits of gs2m_rasterize_depth's alpha, and depth_median > 0 exactly where alpha >= 0.5.
+ * An isotropic Gaussian carries no surface orientation: its t* is the point of the ray nearest the centre, (mu . r) / (r . r),
+ * which is no better a surface estimate than the centre's z.  The gain is for flat Gaussians.
+ *
+ *   depth_expected[H,W], depth_median[H,W], alpha[H,W]   device or NULL, as gs2m_rasterize_depth; all NULL does nothing
+ * Every non-NULL output is written completely with plain stores: two calls give identical bits.  Asynchronous, no host wait
+ * (the first call, and a call with a larger P than any before, allocate the handle's [P] 64-byte ray records).  Only the forward
+ * state is read: a gs2m_rasterize_backward or gs2m_rasterize_depth may follow and gives the bits it gives without this call.
+ * No gradients flow through these maps.
+ *
+ * Errors: those of gs2m_rasterize_depth (no forward state, width / height mismatch, GS2M_OPT_TILE_ROWS 2,
+ * GS2M_OPT_PAIR_BATCH > 1, an overflowed forward); P different from the forward's; NULL means3D / scales / rotations /
+ * viewmatrix.  A forward that took cov3D_precomp has no ray depth (the adjugate by minors cancels exactly where it matters:
+ * on flat Gaussians): pass scales and rotations to both.
+ *
+ * STATED TOLERANCE: against an fp64 statement of the definition above on the walk of tests/depth_statement.py
+ * (tests/ray_depth_statement.py), on the pixels gs2m_rasterize_depth's tolerance keeps and where no contributor's ray lies
+ * within about 1.8 degrees of its Gaussian's plane (den / (sum_k |w_k|^2 |r|^2) < 1e-3: num / den loses its digits in fp32),
+ * depth_expected, and depth_median against z_j(p) of the statement's median Gaussian, are within 4 x the error of the SAME
+ * statement evaluated in fp32 plus (8 + 2 sqrt(n)) 2^-24 (n = the longest run of contributors), in max|x - x64| / max|x64| and
+ * in relative L2 (tests/test_raster_depth_ray.py, tests/test_raster_depth_ray_edges.py; figures:
+ * profiles/raster_depth_ray.txt).
+ */
+int gs2m_rasterize_depth_ray(gs2m_raster* r, int P, const float* means3D, const float* scales, float scale_modifier,
+                             const float* rotations, const float* viewmatrix, float tanfovx, float tanfovy,
+                             int width, int height, float* depth_expected, float* depth_median, float* alpha,
+                             gs2m_stream stream);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:26-31,
  * rasterizer_impl.cu:54-66,141-153).  present[P]: device, 1 byte per Gaussian. */
 int gs2m_mark_visible(int P, const float* means3D, const float* viewmatrix,
