@@ -89,6 +89,8 @@ _PROTOS = {
                                       vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "gs2m_rasterize_backward_depth": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32,
                                             f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "gs2m_rasterize_backward_depth_ray": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32,
+                                                f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "gs2m_raster_backward_rows": (i32, [vp, C.POINTER(i64), C.POINTER(i64)]),
     "gs2m_rasterize_depth": (i32, [vp, i32, i32, vp, vp, vp, vp]),
     "gs2m_rasterize_depth_ray": (i32, [vp, i32, vp, vp, f32, vp, vp, f32, f32, i32, i32, vp, vp, vp, vp]),

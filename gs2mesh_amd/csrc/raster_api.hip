@@ -70,6 +70,7 @@ struct gs2m_raster {
     DeviceBuffer<unsigned long long> d_bw_total;   // [1]
     unsigned long long bw_last_rows = 0;  // instance rows of the last backward call
     DeviceBuffer<float4> d_ray;           // [P][4] ray records of gs2m_rasterize_depth_ray (raster_depth_ray.h), grow-only
+    DeviceBuffer<float> d_bw_rows2;       // [rows][GS2M_BW_ROW] second rows: gs2m_rasterize_backward_depth_ray alone allocates it
     bool fw_valid = false;               // the state is that of ONE gs2m_rasterize_forward call
     int fw_P = 0, fw_W = 0, fw_H = 0, fw_tile_rows = 1;
     // last call
@@ -493,7 +494,9 @@ extern "C" int gs2m_rasterize_forward(gs2m_raster* r, int P, int D, int M, const
 // are still in the arenas.  Stages: row offsets (scan of the rect areas) -> clear the row buffer -> compositing backward (one row
 // per instance, plain stores) -> per-Gaussian backward (sums the rows, continues to the inputs).
 // Body of gs2m_rasterize_backward (depth = 0: the colour kernels, dL_dpix required) and gs2m_rasterize_backward_depth (depth = 1:
-// the instantiations with the depth / opacity map terms, every upstream map may be null).
+// the instantiations with the depth / opacity map terms, every upstream map may be null) and gs2m_rasterize_backward_depth_ray
+// (depth = 2: the depth instantiation on the ray-Gaussian intersection depth, a second row per instance and a second per-Gaussian
+// kernel; scales and rotations required).
 static int rasterize_backward(gs2m_raster* r, const char* who, int depth, int P, int D, int M, const float* background, int width,
                               int height, const float* means3D, const float* shs, const float* colors_precomp,
                               const float* scales, float scale_modifier, const float* rotations,
@@ -533,6 +536,13 @@ static int rasterize_backward(gs2m_raster* r, const char* who, int depth, int P,
         gs2m_set_error("%s: M = %d SH coefficients < (D+1)^2 = %d, or dL_dsh is NULL", who, M, (D + 1) * (D + 1));
         return 1;
     }
+    if (depth == 2 && (cov3D_precomp || !scales || !rotations)) {
+        gs2m_set_error("%s: NULL scales / rotations (a forward with cov3D_precomp has no ray depth: the intersection needs the "
+                       "factors of the covariance)", who);
+        return 1;
+    }
+    // without a gradient of a depth map the ray depth is never read: the centre instantiation (or the colour kernels) compute it
+    if (depth == 2 && !dL_ddepth_expected && !dL_ddepth_median) depth = (dL_dalpha || !dL_dpix) ? 1 : 0;
     const int saved_debug = r->opt_debug;
     if (debug) r->opt_debug = 1;
     struct Restore {
@@ -563,7 +573,17 @@ static int rasterize_backward(gs2m_raster* r, const char* who, int depth, int P,
     }
     if (r->d_bw_rows.reserve((size_t)(n_rows ? n_rows : 1ull) * GS2M_BW_ROW)) return 1;
     r->bw_last_rows = n_rows;
-    if (n_rows) {
+    if (n_rows && depth == 2) {
+        if (r->d_bw_rows2.reserve((size_t)n_rows * GS2M_BW_ROW) || r->d_ray.reserve((size_t)P * 4)) return 1;
+        GS2M_HIPCHK(hipMemsetAsync(r->d_bw_rows.get(), 0, sizeof(float) * (size_t)n_rows * GS2M_BW_ROW, st));
+        GS2M_HIPCHK(hipMemsetAsync(r->d_bw_rows2.get(), 0, sizeof(float) * (size_t)n_rows * GS2M_BW_ROW, st));
+        gs2m_launch_ray_records(st, recs, P, means3D, scales, scale_modifier, rotations, viewmatrix, r->d_ray.get());
+        if (dbg_check(r, st, "ray records")) return 1;
+        gs2m_launch_blend_backward_ray(st, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, r->d_cams.get(), P, r->last_cap,
+                                       dL_dpix, r->d_bw_offset.get(), r->d_bw_rows.get(), r->d_bw_rows2.get(), n_rows,
+                                       r->d_ray.get(), dL_ddepth_expected, dL_ddepth_median, dL_dalpha);
+        if (dbg_check(r, st, "blend backward ray")) return 1;
+    } else if (n_rows) {
         // rows no wave writes (instances behind every pixel's last contributor, tiles a cull level dropped) must read as zero
         GS2M_HIPCHK(hipMemsetAsync(r->d_bw_rows.get(), 0, sizeof(float) * (size_t)n_rows * GS2M_BW_ROW, st));
         gs2m_launch_blend_backward(st, gx, gy, r->d_keys.get(), r->d_tile_start.get(), recs, r->d_cams.get(), P, r->last_cap, dL_dpix, r->d_bw_offset.get(),
@@ -584,6 +604,10 @@ static int rasterize_backward(gs2m_raster* r, const char* who, int depth, int P,
     o.dL_drot = dL_drot;
     gs2m_launch_gaussian_backward(st, g, r->d_cams.get(), recs, r->d_bw_offset.get(), r->d_bw_rows.get(), n_rows, o, depth);
     if (dbg_check(r, st, "gaussian backward")) return 1;
+    if (n_rows && depth == 2) {
+        gs2m_launch_gaussian_backward_ray(st, g, r->d_cams.get(), recs, r->d_bw_offset.get(), r->d_bw_rows2.get(), n_rows, o);
+        if (dbg_check(r, st, "gaussian backward ray")) return 1;
+    }
     return 0;
 }
 
@@ -616,6 +640,24 @@ extern "C" int gs2m_rasterize_backward_depth(gs2m_raster* r, int P, int D, int M
     (void)R;
     const int depth = (dL_ddepth_expected || dL_ddepth_median || dL_dalpha || !dL_dpix) ? 1 : 0;
     return rasterize_backward(r, "gs2m_rasterize_backward_depth", depth, P, D, M, background, width, height, means3D, shs,
+                              colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                              tan_fovx, tan_fovy, dL_dpix, dL_ddepth_expected, dL_ddepth_median, dL_dalpha, dL_dmean2D, dL_dconic,
+                              dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream);
+}
+
+// The same backward with gradients through the maps of gs2m_rasterize_depth_ray (the derivative: include/gs2mesh_amd.h).  With
+// dL_ddepth_expected and dL_ddepth_median both null no ray depth is read and the call IS gs2m_rasterize_backward_depth.
+extern "C" int gs2m_rasterize_backward_depth_ray(gs2m_raster* r, int P, int D, int M, int R, const float* background, int width,
+                                                 int height, const float* means3D, const float* shs, const float* colors_precomp,
+                                                 const float* scales, float scale_modifier, const float* rotations,
+                                                 const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                                 const float* cam_pos, float tan_fovx, float tan_fovy, const float* dL_dpix,
+                                                 const float* dL_ddepth_expected, const float* dL_ddepth_median,
+                                                 const float* dL_dalpha, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                                 float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                                                 float* dL_dscale, float* dL_drot, int debug, gs2m_stream stream) {
+    (void)R;
+    return rasterize_backward(r, "gs2m_rasterize_backward_depth_ray", 2, P, D, M, background, width, height, means3D, shs,
                               colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
                               tan_fovx, tan_fovy, dL_dpix, dL_ddepth_expected, dL_ddepth_median, dL_dalpha, dL_dmean2D, dL_dconic,
                               dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream);

@@ -43,8 +43,43 @@
 // recorded where the depth pass records its z, so D has the forward's bits and the median is the forward's instance.  Values
 // nine and ten share one 2-value butterfly (bw_reduce2).  The DEPTH = false instantiation is the colour backward unchanged: its
 // walk_step carries no S, Z or median, and it neither reads nor writes row[9].
+//
+// Gradients through the RAY maps (k_blend_backward<WPB, true, true>, gs2m_rasterize_backward_depth_ray; the derivative is stated in
+// include/gs2mesh_amd.h).  The depth of instance j at pixel p is z_j(p) = ray_depth() of the staged ray record
+// (raster_depth_ray.h), brought to LDS by walk_gather's `extra` hook as k_blend_depth<WPB, true> does, so walk 1's D and median
+// instance have the bits of gs2m_rasterize_depth_ray and u_j = (gD / S)(z_j(p) - D).  h = dL/dz_j(p), the amount the centre
+// instantiation adds to row[9], goes where ray_depth() took z_j(p) from (ray_branch() repeats its decisions on its bits):
+//   * t = num / den, lo <= t <= hi: ten moments  A += (h / den) r,  Bm += (h t / den) r r^T  (r = (rx, ry, 1); Bm in the order
+//     xx, xy, x, yy, y, 1) -- dt/dc_k = u_k / den and dt/dw_k = ((c_k - 2 t u_k) / den) r summed over the pixels;
+//   * the fallback t = z_c, and a clamp at hi or at lo = z_c - 4 sz: h to row[9]; the clamps also add +-4 h to dL/dsz;
+//   * a clamp at the 0.2 floor: nothing.
+// The eleven values are the instance's SECOND row, at rows2 + row * GS2M_BW_ROW: {A (3), Bm (6), dL/dsz, 0, 0}, reduced with one
+// more bw_reduce8, one bw_reduce2 (Bm's last value and dL/dsz) and stored by lanes 0..9 as the first row is.  Written by the plain stores of
+// the wave that wrote the first row, in an arena only this entry allocates and clears.  Without RAY nothing of this exists: the
+// two other instantiations are the kernels they were.
 #pragma once
+#include "raster_depth_ray.h"
 #include "raster_tile_walk.h"
+
+// where ray_depth() took z_j(p) from: 0 the quotient t (lo <= t <= hi), 1 the fallback z_c, 2 the clamp at hi, 3 the clamp at
+// lo = z_c - 4 sz, 4 the clamp at the 0.2 floor.  Same operations as ray_depth(), so the same bits decide; *t_out and *den_out are
+// its quotient and denominator (read for branch 0 only).
+GS2M_DEVICE int ray_branch(const float4 w0, const float4 w1, const float4 w2, const float4 lim, const float zc, const float rx,
+                           const float ry, float* t_out, float* den_out) {
+    const float u0 = fmaf(w0.x, rx, fmaf(w0.y, ry, w0.z));
+    const float u1 = fmaf(w1.x, rx, fmaf(w1.y, ry, w1.z));
+    const float u2 = fmaf(w2.x, rx, fmaf(w2.y, ry, w2.z));
+    const float num = fmaf(w0.w, u0, fmaf(w1.w, u1, w2.w * u2));
+    const float den = fmaf(u0, u0, fmaf(u1, u1, u2 * u2));
+    const float q = num / den;
+    const bool quotient = den > 0.0f && fabsf(q) <= 3.402823466e+38f;
+    const float t = quotient ? q : zc;
+    *t_out = t;
+    *den_out = den;
+    if (t > lim.y) return 2;
+    if (t < lim.x) return lim.x > 0.2f ? 3 : 4;   // lo = max(z_c - 4 sz, 0.2): above the floor it is z_c - 4 sz
+    return quotient ? 0 : 1;
+}
 
 // sum over the 64 lanes of eight per-lane values: afterwards lane l holds the complete sum of value 4 (l & 1) + 2 ((l >> 1) & 1) +
 // ((l >> 2) & 1).  Each step halves the values a lane carries (it keeps one half, sends the other to its partner): 4 + 2 + 1
@@ -93,12 +128,14 @@ struct BwDepthGrads {
 
 // grid: ceil(tiles / WPB) workgroups of WPB waves; wave w of workgroup b composites tile b * WPB + w of the (single) view.
 // DEPTH = false is the colour backward (gs2m_rasterize_backward): dg is not read and row value 9 is not written.
-template <int WPB, bool DEPTH>
+// RAY (with DEPTH): z_j(p) is the ray-Gaussian intersection depth; `ray` = the records of k_ray_records, `rows2` = the second rows
+template <int WPB, bool DEPTH, bool RAY = false>
 GS2M_KERNEL void __launch_bounds__(64 * WPB)
 k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ tile_start, const GeomRecs recs,
                  const CamUniform* __restrict__ cams, int P, unsigned cap, const float* __restrict__ dL_dpix,
                  const unsigned* __restrict__ row_offset, float* __restrict__ rows, unsigned long long n_rows,
-                 const BwDepthGrads dg) {
+                 const BwDepthGrads dg, const float4* __restrict__ ray = nullptr, float* __restrict__ rows2 = nullptr) {
+    static_assert(DEPTH || !RAY, "the ray instantiation is a depth instantiation");
     // staged instance: a = {mx, my, ca, cb}, b = {cc, op, r, g}, c = {b, row index (bits)}; DEPTH: z = view-space depth
     __shared__ float4 s_a[WPB][64], s_b[WPB][64];
     __shared__ float2 s_c[WPB][64];
@@ -123,6 +160,18 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
     // D in sZ
     float sS[4], sZ[4], gM[4];
     int medpos[4];
+    float4* sr = nullptr;
+    float rx[4], ry[4];
+    if constexpr (RAY) {
+        // vector v of instance j of wave w at s_r[w][v][j], as k_blend_depth<WPB, true> stages it
+        __shared__ float4 s_r[WPB][GS2M_RAY_REC][64];
+        sr = &s_r[t.wave][0][0];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            rx[k] = ray_dir(t.pxf[k], W, cam.tanfovx);
+            ry[k] = ray_dir(t.pyf[k], H, cam.tanfovy);
+        }
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const bool inside = t.inside[k];
@@ -154,6 +203,12 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
             c.x = rc.x;
             c.y = __uint_as_float(row);
             sc[lane] = c;
+            if constexpr (RAY) {   // an id the forward cannot have written stages a zero record (raster_depth.h)
+                const bool known = (unsigned)(keys[base + lane] & 0xffffffffull) < (unsigned)P;
+#pragma unroll
+                for (int v = 0; v < GS2M_RAY_REC; ++v)
+                    sr[64 * v + lane] = known ? ray[GS2M_RAY_REC * (size_t)gid + v] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
         });
     };
     // ---- walk 1, front to back: T_final and n_contrib of every pixel (forward.cu:324-357)
@@ -166,6 +221,15 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
             float z = 0.0f;
             if constexpr (DEPTH) z = sz[j];
             const int pos = (int)(base - r0) + j + 1;
+            if constexpr (RAY) {
+                const float4 w0 = sr[j], w1 = sr[64 + j], w2 = sr[128 + j], lim = sr[192 + j];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float zp = ray_depth(w0, w1, w2, lim, z, rx[k], ry[k]);
+                    walk_step<true, true>(A, B, zp, t.pxf[k], t.pyf[k], T[k], done[k], sS[k], sZ[k], medpos[k], pos, &ncontrib[k], pos);
+                }
+                continue;
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k)   // DEPTH = false: sS, sZ and medpos are not initialised, and walk_step does not touch them
                 walk_step<DEPTH, true>(A, B, z, t.pxf[k], t.pyf[k], T[k], done[k], sS[k], sZ[k], medpos[k], pos, &ncontrib[k], pos);
@@ -222,6 +286,17 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
             float acc[8], acc8 = 0.0f, acc9 = 0.0f;   // mx my ca cb cc op r g | b | z (DEPTH)
             float z = 0.0f;
             if constexpr (DEPTH) z = sz[j];
+            // RAY: the second row {A (3), Bm xx xy x yy y} | {Bm 1, dL/dsz}
+            float mo[8], mo8 = 0.0f, dsz = 0.0f;
+            float4 w0, w1, w2, lim;
+            if constexpr (RAY) {
+                w0 = sr[j];
+                w1 = sr[64 + j];
+                w2 = sr[128 + j];
+                lim = sr[192 + j];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) mo[i] = 0.0f;
+            }
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[i] = 0.0f;
             bool any = false;
@@ -241,7 +316,31 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
                     lc1[k] = B.w;
                     lc2[k] = Cc.x;
                     float dL_dalpha = (B.z - ar0[k]) * dp0[k] + (B.w - ar1[k]) * dp1[k] + (Cc.x - ar2[k]) * dp2[k];
-                    if constexpr (DEPTH) {
+                    if constexpr (RAY) {
+                        const float zp = ray_depth(w0, w1, w2, lim, z, rx[k], ry[k]);
+                        const float u = sS[k] * (zp - sZ[k]);
+                        aru[k] = last_alpha[k] * lu[k] + (1.0f - last_alpha[k]) * aru[k];
+                        lu[k] = u;
+                        dL_dalpha += u - aru[k];
+                        const float h = w * sS[k] + (idx + 1 == medpos[k] ? gM[k] : 0.0f);
+                        float tq, den;
+                        const int br = ray_branch(w0, w1, w2, lim, z, rx[k], ry[k], &tq, &den);
+                        if (br == 0) {
+                            const float hd = h / den, ht = hd * tq;
+                            mo[0] += hd * rx[k];
+                            mo[1] += hd * ry[k];
+                            mo[2] += hd;
+                            mo[3] += ht * rx[k] * rx[k];
+                            mo[4] += ht * rx[k] * ry[k];
+                            mo[5] += ht * rx[k];
+                            mo[6] += ht * ry[k] * ry[k];
+                            mo[7] += ht * ry[k];
+                            mo8 += ht;
+                        } else if (br != 4) {
+                            acc9 += h;
+                            dsz += br == 2 ? 4.0f * h : (br == 3 ? -4.0f * h : 0.0f);
+                        }
+                    } else if constexpr (DEPTH) {
                         const float u = sS[k] * (z - sZ[k]);
                         aru[k] = last_alpha[k] * lu[k] + (1.0f - last_alpha[k]) * aru[k];
                         lu[k] = u;
@@ -275,6 +374,15 @@ k_blend_backward(const unsigned long long* __restrict__ keys, const unsigned* __
                 // lane l < 8 holds value 4 (l & 1) + 2 ((l >> 1) & 1) + ((l >> 2) & 1); lane 8 stores the ninth
                 if (lane < 8) dst[4 * (lane & 1) + 2 * ((lane >> 1) & 1) + ((lane >> 2) & 1)] = s;
                 else if (lane == 8 || (DEPTH && lane == 9)) dst[lane] = s8;   // lane 9 (odd) holds the tenth value
+            }
+            if constexpr (RAY) {
+                const float m = bw_reduce8(mo, lane);
+                const float m8 = bw_reduce2(mo8, dsz, lane);   // even lanes: Bm's last value; odd lanes: dL/dsz
+                if (row < n_rows) {
+                    float* dst = rows2 + (size_t)row * GS2M_BW_ROW;
+                    if (lane < 8) dst[4 * (lane & 1) + 2 * ((lane >> 1) & 1) + ((lane >> 2) & 1)] = m;
+                    else if (lane == 8 || lane == 9) dst[lane] = m8;
+                }
             }
         }
     }

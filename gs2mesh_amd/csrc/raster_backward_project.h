@@ -361,3 +361,139 @@ k_gaussian_backward(GaussIn g, const CamUniform* __restrict__ cams, GeomRecs rec
 #pragma unroll
     for (int k = 0; k < 4; ++k) o.dL_drot[4 * (size_t)i + k] = drot[k];
 }
+
+// Per-Gaussian half of the gradients through the RAY maps (gs2m_rasterize_backward_depth_ray; the derivative is stated in
+// include/gs2mesh_amd.h).  Runs after k_gaussian_backward<true>, which has written every output row and has taken row[9] -- the
+// fallback's and the clamps' dL/dz_c -- to dL/dmean3D; this kernel ADDS what the second rows hold to dL_dmean3D, dL_dscale and
+// dL_drot of the Gaussians the forward listed.  One thread per Gaussian: it sums the second rows {A (3), Bm (6), dL/dsz} in slot
+// order (bitwise reproducible), recomputes R, M, mu, g and sz with the operations of k_ray_records, and applies the chain
+//     dL/dc_k = w_k . A;   dL/dw_k = c_k A - 2 Bm w_k + dL/dc_k mu;   dL/dmu = sum_k dL/dc_k w_k;
+//     w_k = f_k M[:,k], f_k = g_k / gmax, differentiated THROUGH gmax = g_m:  dL/dg_k = dL/df_k / gmax for k != m and
+//     dL/dg_m = -(sum_{k != m} f_k dL/df_k) / gmax.  t is invariant under a common scaling of all (w_k, c_k), so
+//     sum_k f_k dL/df_k = 0 and holding gmax constant gives the same gradient in exact arithmetic; in fp32 it does not:
+//     dL/df_m is what is left of two large sums that cancel, and with gmax held constant that remainder goes straight into
+//     the two large scales of a flat Gaussian.  Through gmax it is never used (f_m = g_m / g_m does not depend on g_m);
+//     g = (s1 s2, s0 s2, s0 s1);
+//     sz = sqrt(sum_k (s_k M[2][k])^2): the derivative through the square root is taken as 0 where the sum is 0;
+//     M = W R(q) -> dL/dR -> dL/dq with q as given;   mu = W x + t -> dL/dmean3D;   s = mod scales: dL/dscale keeps the factor mod.
+// A Gaussian whose ten sums are all zero (no pixel took its depth from the quotient or a clamp) is left as it is: its outputs keep
+// the bits of the alpha path.
+GS2M_KERNEL void __launch_bounds__(256)
+k_gaussian_backward_ray(GaussIn g, const CamUniform* __restrict__ cams, GeomRecs recs, const unsigned* __restrict__ row_offset,
+                        const float* __restrict__ rows2, unsigned long long n_rows, BwOut o) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= g.P) return;
+    const unsigned n = bw_rect_area(recs.c[i]);
+    if (n == 0u) return;   // in no list: no rows
+    float m[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) m[k] = 0.0f;
+    const unsigned long long first = row_offset[i];
+    for (unsigned s = 0; s < n && first + s < n_rows; ++s) {
+        const float4* r4 = reinterpret_cast<const float4*>(rows2 + (size_t)(first + s) * GS2M_BW_ROW);
+        const float4 a = r4[0], b = r4[1];
+        const float2 c = make_float2(r4[2].x, r4[2].y);
+        m[0] += a.x;
+        m[1] += a.y;
+        m[2] += a.z;
+        m[3] += a.w;
+        m[4] += b.x;
+        m[5] += b.y;
+        m[6] += b.z;
+        m[7] += b.w;
+        m[8] += c.x;
+        m[9] += c.y;
+    }
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) any = any || m[k] != 0.0f;   // a NaN sum counts
+    if (!any) return;
+    const float* vm = cams[0].view;
+    const float mod = g.scale_modifier;
+    const float s[3] = {mod * g.scales[3 * (size_t)i], mod * g.scales[3 * (size_t)i + 1], mod * g.scales[3 * (size_t)i + 2]};
+    const float r = g.rots[4 * (size_t)i], x = g.rots[4 * (size_t)i + 1], y = g.rots[4 * (size_t)i + 2], z = g.rots[4 * (size_t)i + 3];
+    const float R[3][3] = {{1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y)},
+                           {2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x)},
+                           {2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y)}};
+    float M[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) M[a][k] = vm[a] * R[0][k] + vm[4 + a] * R[1][k] + vm[8 + a] * R[2][k];
+    const float px = g.xyz[3 * (size_t)i], py = g.xyz[3 * (size_t)i + 1], pz = g.xyz[3 * (size_t)i + 2];
+    const float mu[3] = {vm[0] * px + vm[4] * py + vm[8] * pz + vm[12], vm[1] * px + vm[5] * py + vm[9] * pz + vm[13],
+                         vm[2] * px + vm[6] * py + vm[10] * pz + vm[14]};
+    const float gk[3] = {s[1] * s[2], s[0] * s[2], s[0] * s[1]};
+    const float gmax = fmaxf(gk[0], fmaxf(gk[1], gk[2]));
+    const bool oriented = gmax > 0.0f && gmax <= 3.402823466e+38f;
+    const float A[3] = {m[0], m[1], m[2]};
+    // Bm, symmetric: xx xy x / xy yy y / x y 1
+    const float Bm[3][3] = {{m[3], m[4], m[5]}, {m[4], m[6], m[7]}, {m[5], m[7], m[8]}};
+    float dM[3][3], ds[3] = {0.0f, 0.0f, 0.0f}, dmu[3] = {0.0f, 0.0f, 0.0f}, dg[3] = {0.0f, 0.0f, 0.0f};
+    const int kmax = (gk[0] >= gk[1] && gk[0] >= gk[2]) ? 0 : (gk[1] >= gk[2] ? 1 : 2);   // gmax = g[kmax]
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dM[a][k] = 0.0f;
+    if (oriented) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float f = gk[k] / gmax;
+            const float w[3] = {f * M[0][k], f * M[1][k], f * M[2][k]};
+            const float c = w[0] * mu[0] + w[1] * mu[1] + w[2] * mu[2];
+            const float dc = w[0] * A[0] + w[1] * A[1] + w[2] * A[2];
+            float df = 0.0f;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float Bw = Bm[a][0] * w[0] + Bm[a][1] * w[1] + Bm[a][2] * w[2];
+                const float dw = c * A[a] - 2.0f * Bw + dc * mu[a];
+                dmu[a] += dc * w[a];
+                dM[a][k] = f * dw;
+                df += dw * M[a][k];
+            }
+            dg[k] = df;
+        }
+        // through gmax: f_kmax is 1 whatever g[kmax] is, and g[kmax] divides the other two
+        float through = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) through += k == kmax ? 0.0f : (gk[k] / gmax) * dg[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dg[k] = (k == kmax ? -through : dg[k]) / gmax;
+        ds[0] = dg[1] * s[2] + dg[2] * s[1];
+        ds[1] = dg[0] * s[2] + dg[2] * s[0];
+        ds[2] = dg[0] * s[1] + dg[1] * s[0];
+    }
+    const float a0 = s[0] * M[2][0], a1 = s[1] * M[2][1], a2 = s[2] * M[2][2];
+    const float var = a0 * a0 + a1 * a1 + a2 * a2;
+    if (var > 0.0f) {   // sz = sqrt(var); at var == 0 the derivative through the square root is taken as 0
+        const float ak[3] = {a0, a1, a2};
+        const float k_sz = m[9] / sqrtf(var);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float da = k_sz * ak[k];
+            ds[k] += da * M[2][k];
+            dM[2][k] += da * s[k];
+        }
+    }
+    // M = W R: dL/dR[b][k] = sum_a W[a][b] dL/dM[a][k], W[a][b] = vm[4 b + a]
+    float dR[3][3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dR[b][k] = vm[4 * b] * dM[0][k] + vm[4 * b + 1] * dM[1][k] + vm[4 * b + 2] * dM[2][k];
+    float drot[4];
+    drot[0] = 2.f * (-z * dR[0][1] + y * dR[0][2] + z * dR[1][0] - x * dR[1][2] - y * dR[2][0] + x * dR[2][1]);
+    drot[1] = 2.f * (y * dR[0][1] + z * dR[0][2] + y * dR[1][0] - r * dR[1][2] + z * dR[2][0] + r * dR[2][1]) -
+              4.f * x * (dR[1][1] + dR[2][2]);
+    drot[2] = 2.f * (x * dR[0][1] + r * dR[0][2] + x * dR[1][0] + z * dR[1][2] - r * dR[2][0] + z * dR[2][1]) -
+              4.f * y * (dR[0][0] + dR[2][2]);
+    drot[3] = 2.f * (-r * dR[0][1] + x * dR[0][2] + r * dR[1][0] + y * dR[1][2] + x * dR[2][0] + y * dR[2][1]) -
+              4.f * z * (dR[0][0] + dR[1][1]);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        o.dL_dmean3D[3 * (size_t)i + b] += vm[4 * b] * dmu[0] + vm[4 * b + 1] * dmu[1] + vm[4 * b + 2] * dmu[2];
+        o.dL_dscale[3 * (size_t)i + b] += mod * ds[b];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o.dL_drot[4 * (size_t)i + k] += drot[k];
+}

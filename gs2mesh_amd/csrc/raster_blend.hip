@@ -63,6 +63,18 @@ void gs2m_launch_blend_backward(hipStream_t st, int gx, int gy, const unsigned l
                     dL_dpix, row_offset, rows, n_rows, dg);
 }
 
+// the depth instantiation with the ray-Gaussian intersection depth (gs2m_rasterize_backward_depth_ray): `ray` = the records of
+// gs2m_launch_ray_records, rows2 = the second row of every instance (cleared like `rows`)
+void gs2m_launch_blend_backward_ray(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
+                                    GeomRecs recs, const CamUniform* cams, int P, unsigned cap, const float* dL_dpix,
+                                    const unsigned* row_offset, float* rows, float* rows2, unsigned long long n_rows,
+                                    const float4* ray, const float* dL_ddepth, const float* dL_dmedian, const float* dL_dalpha) {
+    const int tiles = gx * gy;
+    const BwDepthGrads dg{dL_ddepth, dL_dmedian, dL_dalpha};
+    GS2M_LAUNCH((k_blend_backward<4, true, true>), dim3((tiles + 3) / 4), dim3(256), 0, st, keys, tile_start, recs, cams, P, cap,
+                dL_dpix, row_offset, rows, n_rows, dg, ray, rows2);
+}
+
 // depth / opacity maps of the last single-view forward (16 x 16 lists): one wave per tile, four tiles per workgroup
 void gs2m_launch_blend_depth(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
                              GeomRecs recs, int P, unsigned cap, int W, int H, float* depth_expected, float* depth_median,

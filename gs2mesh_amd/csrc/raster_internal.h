@@ -67,6 +67,16 @@ void gs2m_launch_blend_backward(hipStream_t st, int gx, int gy, const unsigned l
 void gs2m_launch_gaussian_backward(hipStream_t st, const GaussIn& g, const CamUniform* cams, GeomRecs recs,
                                    const unsigned* row_offset, const float* rows, unsigned long long n_rows, const BwOut& out,
                                    int depth);
+// ---- gradients through the ray maps (gs2m_rasterize_backward_depth_ray).  The compositing half is the depth instantiation with
+// z_j(p) of the ray records and a second row of GS2M_BW_ROW floats per instance in rows2 (raster_backward_blend.h); the
+// per-Gaussian half runs AFTER gs2m_launch_gaussian_backward(depth = 1) and adds to dL_dmean3D, dL_dscale and dL_drot.
+void gs2m_launch_blend_backward_ray(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,
+                                    GeomRecs recs, const CamUniform* cams, int P, unsigned cap, const float* dL_dpix,
+                                    const unsigned* row_offset, float* rows, float* rows2, unsigned long long n_rows,
+                                    const float4* ray, const float* dL_ddepth, const float* dL_dmedian, const float* dL_dalpha);
+void gs2m_launch_gaussian_backward_ray(hipStream_t st, const GaussIn& g, const CamUniform* cams, GeomRecs recs,
+                                       const unsigned* row_offset, const float* rows2, unsigned long long n_rows,
+                                       const BwOut& out);
 
 // ---- depth / opacity maps (gs2m_rasterize_depth): [H,W] f32 each, any of them null
 void gs2m_launch_blend_depth(hipStream_t st, int gx, int gy, const unsigned long long* keys, const unsigned* tile_start,

@@ -129,3 +129,9 @@ void gs2m_launch_gaussian_backward(hipStream_t st, const GaussIn& g, const CamUn
     else
         GS2M_LAUNCH((k_gaussian_backward<false>), dim3((g.P + 255) / 256), dim3(256), 0, st, g, cams, recs, row_offset, rows, n_rows, out);
 }
+
+void gs2m_launch_gaussian_backward_ray(hipStream_t st, const GaussIn& g, const CamUniform* cams, GeomRecs recs,
+                                       const unsigned* row_offset, const float* rows2, unsigned long long n_rows,
+                                       const BwOut& out) {
+    GS2M_LAUNCH(k_gaussian_backward_ray, dim3((g.P + 255) / 256), dim3(256), 0, st, g, cams, recs, row_offset, rows2, n_rows, out);
+}

@@ -133,8 +133,8 @@ def _function_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotat
     return h, color, radii
 
 
-def _function_backward(ctx, grad_color, **map_grads):
-    """Backward of both autograd Functions: one ``Rasterizer.backward`` call with the upstream gradient of the image and, for the
+def _function_backward(ctx, grad_color, ray_depth=False, **map_grads):
+    """Backward of the autograd Functions (``ray_depth``: the maps are the ray maps, ``Rasterizer.backward(ray_depth=True)``): one ``Rasterizer.backward`` call with the upstream gradient of the image and, for the
     depth Function, of the maps (``grad_depth`` / ``grad_median`` / ``grad_alpha``).  If another forward (or ``render_views``)
     has overwritten the handle's state since ours -- two forwards before one backward, several views per optimiser step, another
     user of the handle -- ours is replayed first into a scratch image.  With ``raster_settings.debug`` a failure leaves the
@@ -150,7 +150,8 @@ def _function_backward(ctx, grad_color, **map_grads):
         if h.state_calls != ctx.state_calls:
             h.forward(_f32c(means3D), _f32c(opacities).reshape(-1), *cam, prefiltered=bool(rs.prefiltered), **args)
             ctx.state_calls = h.state_calls
-        return h.backward(opt(grad_color), _f32c(means3D), *cam, **{k: opt(v) for k, v in map_grads.items()}, **args)
+        more = dict(ray_depth=True) if ray_depth else {}
+        return h.backward(opt(grad_color), _f32c(means3D), *cam, **{k: opt(v) for k, v in map_grads.items()}, **more, **args)
 
     if rs.debug:
         keep = tuple(t.detach().cpu().clone() if isinstance(t, torch.Tensor) else t for t in (
@@ -208,6 +209,31 @@ class _RasterizeGaussiansDepth(torch.autograd.Function):
         return _function_backward(ctx, grad_color, grad_depth=grad_expected, grad_median=grad_median, grad_alpha=grad_alpha)
 
 
+class _RasterizeGaussiansRayDepth(torch.autograd.Function):
+    """``_RasterizeGaussiansDepth`` with the RAY maps: ``expected`` and ``median`` are those of ``depth_maps_ray`` (the depth at
+    which the pixel's ray meets each contributing Gaussian) and the backward is ``gs2m_rasterize_backward_depth_ray``, through
+    which a depth loss reaches rotations and scales by the geometry of the intersection.  Needs scales and rotations."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        rs = raster_settings
+        h, color, radii = _function_forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs)
+        maps = h.depth_maps_ray(_f32c(means3D), _f32c(scales), _f32c(rotations), _f32c(rs.viewmatrix), int(rs.image_width),
+                                int(rs.image_height), float(rs.tanfovx), float(rs.tanfovy),
+                                scale_modifier=float(rs.scale_modifier), like=color)
+        ctx.set_materialize_grads(False)
+        return color, radii, maps["expected"], maps["median"], maps["alpha"]
+
+    @staticmethod
+    def backward(ctx, grad_color, _, grad_expected, grad_median, grad_alpha):
+        if grad_color is None and grad_expected is None and grad_median is None and grad_alpha is None:
+            rs = ctx.raster_settings
+            grad_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32,
+                                     device=ctx.saved_tensors[1].device)
+        return _function_backward(ctx, grad_color, ray_depth=True, grad_depth=grad_expected, grad_median=grad_median,
+                                  grad_alpha=grad_alpha)
+
+
 class GaussianRasterizer(nn.Module):
     """DGR/diff_gaussian_rasterization/__init__.py:171-220."""
 
@@ -225,9 +251,11 @@ class GaussianRasterizer(nn.Module):
         return present.to(torch.bool)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, return_depth=False):
+                cov3D_precomp=None, return_depth=False, ray_depth=False):
         """``return_depth=True`` (an extension; the reference returns ``(color, radii)``): ``(color, radii, expected, median,
-        alpha)`` with the [H,W] maps of ``depth_maps``, carrying the graph when gradients are wanted."""
+        alpha)`` with the [H,W] maps of ``depth_maps``, carrying the graph when gradients are wanted.  With ``ray_depth=True``
+        as well the two depth maps are ``expected_ray`` and ``median_ray`` (``gs2m_rasterize_depth_ray``; scales and rotations
+        required) and their graph is ``gs2m_rasterize_backward_depth_ray``."""
         raster_settings = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -244,19 +272,27 @@ class GaussianRasterizer(nn.Module):
             rotations = torch.Tensor([])
         if cov3D_precomp is None:
             cov3D_precomp = torch.Tensor([])
+        if ray_depth and not return_depth:
+            raise ValueError("ray_depth=True selects the maps of return_depth=True")
+        if ray_depth and (scales.numel() == 0 or rotations.numel() == 0):
+            raise ValueError("ray_depth=True needs scales and rotations: a forward with cov3D_precomp has no ray depth")
         # Invoke the HIP rasterization routine
         tensors = (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)
         with_graph = return_depth and torch.is_grad_enabled() and any(
             isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
         if with_graph:
-            out = _RasterizeGaussiansDepth.apply(*tensors, raster_settings)
+            out = (_RasterizeGaussiansRayDepth if ray_depth else _RasterizeGaussiansDepth).apply(*tensors, raster_settings)
         else:
             out = rasterize_gaussians(*tensors, raster_settings)
         h = _handle(means3D.device)
         self._last = (h, h.state_calls, tensors[:1] + tensors[2:])
         if return_depth and not with_graph:
-            maps = self.depth_maps()
-            out = (*out, maps["expected"], maps["median"], maps["alpha"])
+            if ray_depth:
+                maps = self.depth_maps(("expected_ray", "median_ray", "alpha"))
+                out = (*out, maps["expected_ray"], maps["median_ray"], maps["alpha"])
+            else:
+                maps = self.depth_maps()
+                out = (*out, maps["expected"], maps["median"], maps["alpha"])
         return out
 
     def depth_maps(self, want=("expected", "median", "alpha")):
@@ -270,7 +306,8 @@ class GaussianRasterizer(nn.Module):
         ``expected_ray`` and ``median_ray`` are the same two maps with the depth at which the pixel's ray meets each
         contributing Gaussian in place of its centre's z (``gs2m_rasterize_depth_ray``: one more call, from the inputs of the
         last forward).  They need ``scales`` and ``rotations``: after a forward with ``cov3D_precomp`` asking for them raises
-        ``ValueError``.  No gradient flows through them."""
+        ``ValueError``.  Detached like the others; ray maps that carry the graph come from
+        ``forward(..., return_depth=True, ray_depth=True)``."""
         names = ("expected", "median", "alpha")
         ray_names = {"expected_ray": "expected", "median_ray": "median"}
         if self._last is None:

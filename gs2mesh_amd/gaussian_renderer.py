@@ -27,8 +27,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     a loss on them trains the splat; ``viewspace_points.grad`` then includes their screen-space term.
     ``ray_depth=True`` (with ``return_depth``) adds ``ray_depth`` and ``ray_median_depth``: the same two depth maps with the
     depth at which the pixel's ray meets each contributing Gaussian in place of its centre's z (``gs2m_rasterize_depth_ray``) --
-    the plane of a flat Gaussian instead of a staircase.  These two are always DETACHED, also with ``depth_grad=True``, which
-    leaves the other maps and their gradients as they are.  Not available with ``pipe.compute_cov3D_python``."""
+    the plane of a flat Gaussian instead of a staircase.  With ``depth_grad=False`` these two are detached like the others.  With
+    ``depth_grad=True``, where gradients are wanted, THEY carry the graph (``gs2m_rasterize_backward_depth_ray``): a loss on them
+    reaches rotations and scales through the geometry of the intersection, which a loss on ``depth`` cannot; ``alpha`` carries
+    the graph as before, and ``depth`` / ``median_depth`` are then detached (one backward pass per forward).  Not available
+    with ``pipe.compute_cov3D_python``."""
     device = pc.get_xyz.device
     tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
     tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
@@ -73,9 +76,13 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         screenspace_points = torch.zeros_like(means3D)
     inputs = dict(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
                   scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
-    maps = None
+    maps = ray = None
     with torch.enable_grad() if want_grad else torch.no_grad():
-        if return_depth and depth_grad and want_grad:   # the maps are outputs of the autograd Function: they carry the graph
+        if return_depth and depth_grad and want_grad and ray_depth:   # the ray maps and alpha are the Function's outputs
+            rendered_image, radii, expected, median, alpha = rasterizer(**inputs, return_depth=True, ray_depth=True)
+            ray = {"expected_ray": expected, "median_ray": median}
+            maps = dict(rasterizer.depth_maps(want=("expected", "median")), alpha=alpha)
+        elif return_depth and depth_grad and want_grad:   # the maps are outputs of the autograd Function: they carry the graph
             rendered_image, radii, expected, median, alpha = rasterizer(**inputs, return_depth=True)
             maps = {"expected": expected, "median": median, "alpha": alpha}
         else:
@@ -87,6 +94,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
             maps = rasterizer.depth_maps()
         out.update(depth=maps["expected"], median_depth=maps["median"], alpha=maps["alpha"])
         if ray_depth:
-            ray = rasterizer.depth_maps(want=("expected_ray", "median_ray"))
+            if ray is None:
+                ray = rasterizer.depth_maps(want=("expected_ray", "median_ray"))
             out.update(ray_depth=ray["expected_ray"], ray_median_depth=ray["median_ray"])
     return out

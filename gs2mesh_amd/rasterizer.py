@@ -212,12 +212,16 @@ class Rasterizer:
 
     def backward(self, dL_dpix, means3D, viewmatrix, projmatrix, campos, bg, W, H, tanfovx, tanfovy, shs=None,
                  colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, sh_degree=3, scale_modifier=1.0,
-                 debug=False, want_conic=False, stream=None, grad_depth=None, grad_median=None, grad_alpha=None):
+                 debug=False, want_conic=False, stream=None, grad_depth=None, grad_median=None, grad_alpha=None,
+                 ray_depth=False):
         """``gs2m_rasterize_backward``: gradients of the LAST ``forward`` on this handle, which must have been called with
         the same inputs (``state_calls`` tells whether another ``forward`` / ``render_views`` ran since).  ``dL_dpix``
         [3,H,W].  ``grad_depth`` / ``grad_median`` / ``grad_alpha``: [H,W] upstream gradients of the ``depth_maps`` of that
         forward (``expected``, ``median``, ``alpha``); with any of them given the call is ``gs2m_rasterize_backward_depth``,
-        a missing one counts as zeros and ``dL_dpix`` may be None as well.  Returns a dict of freshly allocated arrays: mean2D[P,3] (NDC-scaled, z = 0), opacity[P], color[P,3],
+        a missing one counts as zeros and ``dL_dpix`` may be None as well.  ``ray_depth=True``: ``grad_depth`` and
+        ``grad_median`` are gradients of the maps of ``depth_maps_ray`` and the call is ``gs2m_rasterize_backward_depth_ray``
+        (scales and rotations required): the depth gradient then also reaches ``scale`` and ``rot`` through the ray-Gaussian
+        intersection, where the centre maps' reaches ``mean3D`` alone.  Returns a dict of freshly allocated arrays: mean2D[P,3] (NDC-scaled, z = 0), opacity[P], color[P,3],
         mean3D[P,3], cov3D[P,6], sh[P,M,3] (None with ``colors_precomp``), scale[P,3], rot[P,4], and conic[P,4] with
         ``want_conic``.  Every array is written in full; synchronises the stream once."""
         P = int(means3D.shape[0])
@@ -232,7 +236,10 @@ class Rasterizer:
                  sh=_empty(means3D, (P, M, 3), np.float32) if M else None,
                  conic=_empty(means3D, (P, 4), np.float32) if want_conic else None)
         depth = not (grad_depth is None and grad_median is None and grad_alpha is None)
-        fn = self._lib.gs2m_rasterize_backward_depth if depth else self._lib.gs2m_rasterize_backward
+        if ray_depth:
+            depth, fn = True, self._lib.gs2m_rasterize_backward_depth_ray
+        else:
+            fn = self._lib.gs2m_rasterize_backward_depth if depth else self._lib.gs2m_rasterize_backward
         ups = (_ptr(dL_dpix, f32, "dL_dpix"),)
         if depth:
             ups += (_ptr(grad_depth, f32, "grad_depth"), _ptr(grad_median, f32, "grad_median"),
@@ -277,7 +284,7 @@ class Rasterizer:
         ``depth_maps`` has the z of its centre.  Maps of the LAST ``forward`` on this handle, whose ``means3D``, ``scales``,
         ``rotations``, ``viewmatrix``, ``scale_modifier`` and camera these must be; a forward with ``cov3D_precomp`` has no ray
         depth.  ``alpha`` has the bits of ``depth_maps``' alpha.  -> dict of freshly allocated [H,W] float32 arrays, one per
-        name in ``want``; 0 = no contributor.  Asynchronous; no gradients.  ``like``: a tensor on the device the maps go to
+        name in ``want``; 0 = no contributor.  Asynchronous.  Gradients through these maps: ``backward(..., ray_depth=True)``.  ``like``: a tensor on the device the maps go to
         (default: where ``means3D`` lives)."""
         names = ("expected", "median", "alpha")
         unknown = [w for w in want if w not in names]

@@ -61,6 +61,8 @@ class OptimizationParams:
         self.percent_dense = 0.01
         self.lambda_dssim = 0.2
         self.lambda_depth = 0.0             # weight of depth_l1_loss against train(..., depth_priors=...); an extension
+        self.depth_kind = "centre"          # the rendered depth that loss compares: "centre" (z of the centres) or "ray" (the
+                                            # ray-Gaussian intersection depth, whose gradient also turns the Gaussians)
         self.densification_interval = 100
         self.opacity_reset_interval = 3000
         self.densify_from_iter = 500
@@ -227,12 +229,17 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
     has no host wait in its update phase; ``"sparse_adam"`` steps only the rows the view saw (``radii > 0``).
     ``depth_priors``: None, or one [H,W] depth map per camera on the device (view-space z, 0 = invalid; e.g. what ``Stereo`` or
     ``RenderedDepth`` wrote).  With priors and ``opt.lambda_depth > 0`` every iteration renders with ``depth_grad=True`` and adds
-    ``opt.lambda_depth * depth_l1_loss(depth, alpha, prior)`` to its loss; otherwise the loop is unchanged."""
+    ``opt.lambda_depth * depth_l1_loss(depth, alpha, prior)`` to its loss; otherwise the loop is unchanged.  ``opt.depth_kind``
+    chooses that depth: ``"centre"`` (the default: ``pkg["depth"]``, through ``gs2m_rasterize_backward_depth``) or ``"ray"``
+    (``pkg["ray_depth"]`` of ``render(..., ray_depth=True)``, through ``gs2m_rasterize_backward_depth_ray``)."""
     if loss not in ("torch", "fused"):
         raise ValueError(f"train: loss must be 'torch' or 'fused', got {loss!r}")
     lambda_depth = float(getattr(opt, "lambda_depth", 0.0)) if depth_priors is not None else 0.0
     if lambda_depth > 0.0 and len(depth_priors) != len(cameras):
         raise ValueError(f"train: {len(depth_priors)} depth priors for {len(cameras)} cameras")
+    depth_kind = getattr(opt, "depth_kind", "centre")
+    if depth_kind not in ("centre", "ray"):
+        raise ValueError(f"train: opt.depth_kind must be 'centre' or 'ray', got {depth_kind!r}")
     from .gaussian_renderer import render
     loss_of = fused_loss if loss == "fused" else loss_fn
     from .optim import FusedAdam
@@ -261,7 +268,8 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
         if opt.random_background:
             background = torch.tensor([rng.random() for _ in range(3)], dtype=torch.float32, device=bg.device)
         if lambda_depth > 0.0:
-            pkg = render(cameras[view], gaussians, pipe, background, return_depth=True, depth_grad=True)
+            pkg = render(cameras[view], gaussians, pipe, background, return_depth=True, depth_grad=True,
+                         ray_depth=depth_kind == "ray")
         else:
             pkg = render(cameras[view], gaussians, pipe, background)
         image, viewspace, visible, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
@@ -269,7 +277,7 @@ def train(gaussians, cameras, images, opt, *, extent, bg, white_background=False
             t.append(mark())
         loss = loss_of(image, images[view], opt.lambda_dssim)
         if lambda_depth > 0.0:
-            loss = loss + lambda_depth * depth_l1_loss(pkg["depth"], pkg["alpha"], depth_priors[view])
+            loss = loss + lambda_depth * depth_l1_loss(pkg["ray_depth" if depth_kind == "ray" else "depth"], pkg["alpha"], depth_priors[view])
         if t:
             t.append(mark())
         loss.backward()

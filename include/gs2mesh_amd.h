@@ -356,6 +356,54 @@ int gs2m_rasterize_depth_ray(gs2m_raster* r, int P, const float* means3D, const 
                              int width, int height, float* depth_expected, float* depth_median, float* alpha,
                              gs2m_stream stream);
 
+/*
+ * Backward of the LAST gs2m_rasterize_forward on this handle with gradients through the maps of gs2m_rasterize_depth_ray: the
+ * argument list of gs2m_rasterize_backward_depth, the three upstream maps being those of the ray maps.  The alpha path is
+ * that call's, with z_j(p) of the ray forward (recomputed by the forward's own function: D and the median instance have the
+ * bits of gs2m_rasterize_depth_ray) where it has z_j:  u_j = (gD / S)(z_j(p) - D).
+ *
+ * What is new is where h = dL/dz_j(p) goes (per instance j and pixel p, h = w_j gD / S, plus gM on the pixel whose median is
+ * j).  In the notation of gs2m_rasterize_depth_ray, r = (rx, ry, 1), u_k = w_k . r, num = sum c_k u_k, den = sum u_k^2:
+ *   - t = num / den taken and lo <= t <= hi:  dt/dc_k = u_k / den,  dt/dw_k = ((c_k - 2 t u_k) / den) r.  Summed over the
+ *     pixels these are ten moments  A = sum (h / den) r  and  Bm = sum (h t / den) r r^T (symmetric), and
+ *         dL/dc_k = w_k . A,    dL/dw_k = c_k A - 2 Bm w_k;
+ *   - the fallback (den > 0 false or a non-finite quotient: t = z_c): h goes to dL/dz_c;
+ *   - t > hi, or t < lo with lo = z_c - 4 sz: h goes to dL/dz_c and +4 h (hi) or -4 h (lo) to dL/dsz -- the derivative of the
+ *     clamp as stated;
+ *   - t < lo with lo the 0.2 floor: no gradient.
+ * Then, per Gaussian: c_k = w_k . mu (to w_k and mu);  w_k = (g_k / gmax) M[:,k], g = (s1 s2, s0 s2, s0 s1), differentiated
+ * THROUGH gmax.  (t is invariant under a common scaling of all (w_k, c_k), so holding gmax constant is the same gradient in
+ * exact arithmetic; through gmax the derivative by the largest g_k, the remainder of two sums that cancel, is never formed.)
+ * sz = sqrt(sum_k s_k^2 M[2][k]^2) to s and row 2 of M, the derivative through the square root taken as 0 where the sum is 0;
+ * mu and z_c to dL_dmean3D through the view rotation;  M = W R(q) to dL_drot with q as given, as computeCov3D's backward
+ * treats it;  s = scale_modifier * scales to dL_dscale, which keeps the factor scale_modifier as in gs2m_rasterize_backward.
+ * The three results are ADDED to what the colour / alpha path writes into dL_dmean3D, dL_dscale and dL_drot.  A centre
+ * depth can only push a Gaussian along the view axis; this derivative also turns it.
+ *
+ * With dL_ddepth_expected and dL_ddepth_median both NULL no depth is read: the call IS gs2m_rasterize_backward_depth, bit for
+ * bit.  Preconditions and errors: those of gs2m_rasterize_backward_depth and of gs2m_rasterize_depth_ray -- cov3D_precomp
+ * non-NULL, or NULL scales or rotations, is an error; on an error nothing is written.  One stream synchronisation.  The ten
+ * moments and dL/dsz are a second 48-byte row per instance, in an arena of their own that only this entry allocates; no
+ * float atomics, every sum in a fixed order: two calls give identical bits.
+ *
+ * STATED TOLERANCE: against the fp64 statement tests/ray_depth_grad_statement.py (tests/depth_grad_statement.py with z_j(p)
+ * of tests/ray_depth_statement.py over leaf tensors), weights zero as for gs2m_rasterize_backward_depth and also on grazing
+ * pixels (gs2m_rasterize_depth_ray's 1e-3) and where a contributor's t lies within 1e-4 relative of lo or hi, every gradient
+ * tensor is within 4 x the error of the SAME statement evaluated in fp32, in max|g - g64| / max|g64| and in relative L2
+ * (tests/test_raster_depth_ray_backward.py, tests/test_raster_depth_ray_backward_edges.py; figures:
+ * profiles/raster_depth_ray_backward.txt).
+ */
+int gs2m_rasterize_backward_depth_ray(gs2m_raster* r, int P, int D, int M, int R, const float* background,
+                                      int width, int height, const float* means3D, const float* shs,
+                                      const float* colors_precomp, const float* scales, float scale_modifier,
+                                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                      const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                                      const float* dL_dpix, const float* dL_ddepth_expected,
+                                      const float* dL_ddepth_median, const float* dL_dalpha, float* dL_dmean2D,
+                                      float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                                      float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug,
+                                      gs2m_stream stream);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:26-31,
  * rasterizer_impl.cu:54-66,141-153).  present[P]: device, 1 byte per Gaussian. */
 int gs2m_mark_visible(int P, const float* means3D, const float* viewmatrix,

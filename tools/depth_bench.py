@@ -9,7 +9,8 @@
   * RenderedDepth.run(keep_on_device=True, write_files=False) + TSDF.run(fuse="batch") over `views` ring cameras, in views/s:
     a host clock around work that ends in the mesh download, after one warm-up pass of the same shapes.
   * the backward pass, in us per view, each call with its one stream synchronisation: gs2m_rasterize_backward (colour only)
-    and gs2m_rasterize_backward_depth with all three map gradients; with --parent-lib (a libgs2mesh_amd.so built from the
+    gs2m_rasterize_backward_depth with all three map gradients and gs2m_rasterize_backward_depth_ray with the same three (on
+    the ray maps; with --parent-lib also against the parent's gs2m_rasterize_backward_depth); with --parent-lib (a libgs2mesh_amd.so built from the
     parent commit) also the parent's gs2m_rasterize_backward on the same inputs, the three ALTERNATING inside every repeat
     (this, parent, depth, parent, this, ...) so that drift of the shared machine hits them alike.  `backward_same_code_spread`
     is the spread of this commit's colour backward against itself (its even repeats over its odd ones): a
@@ -218,14 +219,17 @@ def main():
     g_pix = torch.rand((3, H, W), generator=gen).to(dev) - 0.5
     g_maps = [(torch.rand((H, W), generator=gen).to(dev) - 0.5) for _ in range(3)]
     bw = lambda rr: rr.backward(g_pix, xyz, *common, **kw)
-    bw_depth = lambda: r.backward(g_pix, xyz, *common, grad_depth=g_maps[0], grad_median=g_maps[1], grad_alpha=g_maps[2], **kw)
-    runners = [("backward_us", lambda: bw(r)), ("backward_depth_us", bw_depth)]
+    bw_depth = lambda rr=r, **more: rr.backward(g_pix, xyz, *common, grad_depth=g_maps[0], grad_median=g_maps[1],
+                                                grad_alpha=g_maps[2], **more, **kw)
+    runners = [("backward_us", lambda: bw(r)), ("backward_depth_us", bw_depth),
+               ("backward_depth_ray_us", lambda: bw_depth(ray_depth=True))]
     if a.skip_backward:
         runners = []
     elif a.parent_lib:
         same = all(torch.equal(x, y) for x, y in zip(bw(r).values(), bw(rp).values()) if x is not None)
         runners.insert(1, ("backward_parent_us", lambda: bw(rp)))
-        runners.append(("backward_parent_us", lambda: bw(rp)))       # this, parent, depth, parent
+        runners.insert(3, ("backward_parent_us", lambda: bw(rp)))    # this, parent, depth, parent, ray, parent's depth
+        runners.append(("backward_depth_parent_us", lambda: bw_depth(rp)))
     fwd()
     for _, fn in runners:
         fn()
@@ -268,9 +272,15 @@ def main():
         half = t_bw["backward_us"]
         res["backward_same_code_spread"] = round(statistics.median(half[::2]) / statistics.median(half[1::2]), 4)
         res["backward_depth_over_backward"] = round(statistics.median(t_bw["backward_depth_us"]) / statistics.median(half), 3)
+        res["backward_depth_ray_over_backward_depth"] = round(
+            statistics.median(t_bw["backward_depth_ray_us"]) / statistics.median(t_bw["backward_depth_us"]), 3)
     if a.parent_lib and not a.skip_backward:
         res["backward_over_parent"] = round(statistics.median(half) / statistics.median(t_bw["backward_parent_us"]), 4)
         res["backward_bits_equal_parent"] = bool(same)
+        res["backward_depth_over_parent"] = round(
+            statistics.median(t_bw["backward_depth_us"]) / statistics.median(t_bw["backward_depth_parent_us"]), 4)
+        res["backward_depth_ray_over_parent_backward_depth"] = round(
+            statistics.median(t_bw["backward_depth_ray_us"]) / statistics.median(t_bw["backward_depth_parent_us"]), 3)
     try:
         if a.skip_pipeline:
             raise RuntimeError("skipped (--skip-pipeline)")

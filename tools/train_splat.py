@@ -1,7 +1,7 @@
 """Train a Gaussian splat on one GPU: point cloud + posed images -> point_cloud/iteration_N/point_cloud.ply.
 
     python tools/train_splat.py <colmap_dir> <out_dir> [--iterations N] [--resolution-scale s] [--loss {torch,fused}]
-                                [--optimizer {default,fused,sparse_adam}] [--depth-priors DIR --lambda-depth X]
+                                [--optimizer {default,fused,sparse_adam}] [--depth-priors DIR --lambda-depth X [--depth-kind {centre,ray}]]
     python tools/train_splat.py --synthetic <out_dir> [--iterations N] [--loss {torch,fused}] [--optimizer ...]
 
 <colmap_dir> holds a COLMAP text model (sparse/0/cameras.txt, images.txt, points3D.txt; PINHOLE or SIMPLE_PINHOLE cameras)
@@ -13,7 +13,8 @@ iteration and its split into render forward, loss, backward and optimiser + dens
 torch.optim.Adam and boolean-mask indexing; --optimizer sparse_adam steps only the Gaussians the view saw.
 --depth-priors DIR --lambda-depth X adds X * training.depth_l1_loss against one depth map per camera, read from
 DIR/<NNN>/out_<model>/depth.npy (NNN = the camera's position in the list, the layout `Stereo` and `RenderedDepth` write;
---depth-model names <model>, default the only out_* folder); 0, NaN and inf in a map mean "no depth".
+--depth-model names <model>, default the only out_* folder); 0, NaN and inf in a map mean "no depth".  --depth-kind ray compares the priors with
+the ray-Gaussian intersection depth instead of the z of the centres: its gradient also turns and flattens the Gaussians.
 """
 import argparse
 import json
@@ -95,6 +96,8 @@ def main():
     ap.add_argument("--depth-priors", metavar="DIR", help="folder of <NNN>/out_<model>/depth.npy, one per camera")
     ap.add_argument("--depth-model", default=None, help="<model> of out_<model> under --depth-priors")
     ap.add_argument("--lambda-depth", type=float, default=0.0, help="weight of the depth L1 term (needs --depth-priors)")
+    ap.add_argument("--depth-kind", choices=["centre", "ray"], default="centre",
+                    help="the rendered depth the depth term compares: z of the centres, or the ray-Gaussian intersection depth")
     a = ap.parse_args()
     if (a.lambda_depth > 0) != bool(a.depth_priors):
         ap.error("--depth-priors and a positive --lambda-depth go together")
@@ -115,7 +118,7 @@ def main():
         cameras, images, pcd = load_colmap(a.paths[0], a.resolution_scale, device)
     # schedules written in iterations scale with a short run the way the reference's defaults sit in 30 000
     opt = training.OptimizationParams(iterations=a.iterations, position_lr_max_steps=a.iterations, optimizer_type=a.optimizer,
-                                      lambda_depth=a.lambda_depth)
+                                      lambda_depth=a.lambda_depth, depth_kind=a.depth_kind)
     priors = load_depth_priors(a.depth_priors, cameras, a.depth_model, device) if a.depth_priors else None
     if a.iterations < 30_000:
         f = a.iterations / 30_000
@@ -148,7 +151,7 @@ def main():
     split = {name: statistics.fmean(v) for name, v in timing.items()}
     print(json.dumps({
         "ply": ply, "views": len(cameras), "width": cameras[0].image_width, "height": cameras[0].image_height,
-        "iterations": a.iterations, "loss_path": a.loss, "optimizer": a.optimizer, "lambda_depth": a.lambda_depth, "gaussians_start": P0, "gaussians_end": int(g.get_xyz.shape[0]),
+        "iterations": a.iterations, "loss_path": a.loss, "optimizer": a.optimizer, "lambda_depth": a.lambda_depth, "depth_kind": a.depth_kind, "gaussians_start": P0, "gaussians_end": int(g.get_xyz.shape[0]),
         "loss_first_tenth": statistics.fmean(losses[:k]), "loss_last_tenth": statistics.fmean(losses[-k:]),
         "wall_ms_per_iteration": 1e3 * wall / max(1, a.iterations),
         "stream_ms_per_iteration": {"render_forward": split["render"], "loss": split["loss"], "backward": split["backward"],
